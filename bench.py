@@ -10,6 +10,13 @@ VALs from 2 virtual replicas that also ACK every local write. N>1 (torchrun): on
 GPU, INV/VAL slabs all-gathered and ACKs returned over RCCL (hermes_amd.replica_group).
 
 Prints one JSON line on rank 0 (see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times the steps and prints the headline figure (with the local
+launch's roofline from the HIP events of the timed steps). --full adds every other leg: the
+host-pointer entry point, the CPU baselines, the untimed probe and audit steps (every launch's
+duration and elements, the commit breakdown) and the other refill policies. --dump-outputs DIR
+writes what the last timed step left (DIR/<name>.npy), the same from run to run for the same
+arguments.
 """
 from __future__ import annotations
 
@@ -26,6 +33,8 @@ HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md)
 EVENT_EVERY = 4                # timed steps per sampled local-launch duration
 PROBE_STEPS = 3                # untimed steps with every batch launch timed
 AUDIT_STEPS = 6                # untimed steps whose commits are broken down by outcome (CommitAudit)
+REMOTE_ROUNDS = 64             # the virtual peers' INV / VAL slabs drawn before the steps (Round's default); more
+                               # rounds than that take them again in turn, each under the round's own timestamps
 # algorithmic bytes per element, SURVEY.md 8(d): S_op (56, or 312 big), bucket 64, entry (64, or
 # 320 big), S_msg 16 (ACKs carry S_op with RMWs)
 def elem_bytes(op: int, entry: int, ack: int) -> dict:
@@ -37,20 +46,60 @@ def elem_bytes(op: int, entry: int, ack: int) -> dict:
             "ack": ack + 64 + 2 * meta + ack, "val": 16 + 64 + 2 * meta + 16}
 
 
+def log_rows(kvs, n_keys: int):
+    """The populated log entries [n_keys][entry] as a torch tensor without a copy."""
+    import torch
+
+    class _Dev:   # __cuda_array_interface__ over the library's device pointer
+        def __init__(self, ptr, n):
+            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 3}
+    e = kvs.sizes.entry
+    return torch.as_tensor(_Dev(kvs.device_log(), n_keys * e), device=f"cuda:{kvs.device}").view(n_keys, e)
+
+
+DUMP_ROW_BYTES = 4 << 20       # device bytes per dumped byte array (x4 as float32; three arrays: 48 MiB at most)
+
+
+def dump_outputs(path: str, r, kvs, n_keys: int, seed: int, suffix: str = "") -> None:
+    """What a caller of the round holds after the last timed step, as float32 / float64 .npy files:
+    every op's state byte (the local batch's mirror), the ops themselves (responses and values),
+    the INVs each worker sends, the commit counters, and the table's entries. Arrays
+    larger than DUMP_ROW_BYTES are cut to a seeded sample of their rows (the same rows every run)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(seed)
+
+    def rows(t):   # [n][row bytes] uint8 on the device -> float32 on the host, sampled if large
+        n, keep = t.shape[0], max(1, DUMP_ROW_BYTES // t.shape[1])
+        if n > keep:
+            idx = torch.from_numpy(np.sort(rng.integers(0, n, size=keep))).to(t.device)
+            t = t.index_select(0, idx)
+        return t.to(torch.float32).cpu().numpy()
+
+    W = r.W
+    out = {
+        "op_states": rows(r.states.view(W, -1)),
+        "ops": rows(r.ops.view(-1, r.op)),
+        "table_entries": rows(log_rows(kvs, n_keys)),
+        "inv_count": r.inv_count.to(torch.float32).cpu().numpy(),
+        # committed, misses, writes completed, dropped, RMW aborts since the first warm-up step
+        "counters": r.fold_counters()[:5].to(torch.float64).cpu().numpy(),
+    }
+    for name, arr in out.items():
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
+
+
 def table_digest(kvs, n_keys: int, chunk: int = 1 << 23) -> tuple[int, int]:
     """(digest, keys not VALID) of a replica's protocol state: each populated log entry's state,
     timestamp (cid, version) and value, position-weighted (the populated entries sit back to back
     in the same order on every replica). Equal digests on all replicas = the group converged."""
     import torch
 
-    class _Dev:   # the log as a torch tensor without a copy (__cuda_array_interface__)
-        def __init__(self, ptr, n):
-            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (ptr, False), "version": 3}
-    e = kvs.sizes.entry
     cols = torch.tensor([18] + list(range(23, 28)) + list(range(33, 33 + min(31, kvs.sizes.st_value))),
                         device=f"cuda:{kvs.device}")
     w = (torch.arange(cols.numel(), device=cols.device, dtype=torch.int64) * 0x9E3779B1 + 0x7F4A7C15) | 1
-    log = torch.as_tensor(_Dev(kvs.device_log(), n_keys * e), device=f"cuda:{kvs.device}").view(n_keys, e)
+    log = log_rows(kvs, n_keys)
     dig = torch.zeros((), dtype=torch.int64, device=cols.device)
     bad = torch.zeros((), dtype=torch.int64, device=cols.device)
     for lo in range(0, n_keys, chunk):
@@ -72,6 +121,14 @@ def parse():
                         "one dropped in the middle of the timed steps")
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline figure: the host-pointer entry point, the CPU "
+                        "baselines, the untimed probe and audit steps (every launch's duration, elements per step, "
+                        "commit breakdown) and the other refill policies; a plain run only times the steps")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one left as DIR/<name>.npy (float32 / float64; "
+                        "large arrays as a seeded sample of rows): op states, ops, table entries, INV counts, "
+                        "commit counters (N>1: one set per rank, <name>_rank<r>.npy)")
     p.add_argument("--keys", type=int, default=None,
                    help="keys per replica (default: 100M at N=1, configs[1]; 1B at N>1, configs[3])")
     p.add_argument("--workers", type=int, default=16384,
@@ -81,14 +138,14 @@ def parse():
     p.add_argument("--write-permille", type=int, default=None, help="default 200 (cfg2), 500 (cfg3)")
     p.add_argument("--rmw-permille", type=int, default=None,
                    help="RMWs among the writes, permille (default 0 (cfg2), 500 (cfg3))")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length (0 = skip)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample length (0 = skip)")
     p.add_argument("--cpu-workers", type=int, default=0,
                    help="CPU baseline 250-op buffers (0 = one per thread, as the reference's workers)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU baseline worker threads (0 = one per usable core, at most 16)")
     p.add_argument("--seed", type=int, default=0x5EED)
     p.add_argument("--host-api-seconds", type=float, default=1.0,
-                   help="time the host-pointer entry point for this long (0 = skip; N=1 only)")
+                   help="--full: time the host-pointer entry point for this long (0 = skip; N=1 only)")
     p.add_argument("--no-fit-acks", action="store_true",
                    help="N=1: keep the ACK slab at its capacity stride (2C) instead of the round's largest count")
     p.add_argument("--val-credits", type=int, default=None,
@@ -112,7 +169,7 @@ def parse():
                         "that the next local launch writes into the ops (hkv_wl_refill_plan, the default; configs[2] "
                         "under retry refills in place anyway, where that is faster)")
     p.add_argument("--policy-steps", "--retry-steps", type=int, default=10, dest="policy_steps",
-                   help="N=1: also time this many steps of each other refill policy on the same table and "
+                   help="--full at N=1: also time this many steps of each other refill policy on the same table and "
                         "report them under detail.policies (0 = skip)")
     p.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                    help="torch.distributed backend for N>1 (nccl = RCCL; gloo lets several ranks share one "
@@ -165,7 +222,9 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # the host-pointer callers run first, before this process opens the GPU: with this process's queues
     # idle beside them they measured 6.2 / 23.9 M instead of 7.2-8.1 / 31-34 M (1 / 8 threads)
-    host_api = host_api_rate(a.host_api_seconds) if rank == 0 and world == 1 and a.host_api_seconds > 0 else None
+    host_api = None
+    if a.full and rank == 0 and world == 1 and a.host_api_seconds > 0:
+        host_api = host_api_rate(a.host_api_seconds)
     import torch
     import torch.distributed as dist
 
@@ -209,7 +268,7 @@ def main():
     total_steps = a.warmup + a.steps
     cpu = None
     snaps = {}
-    if rank == 0 and world == 1 and a.cpu_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0:
         # the CPU baseline runs on the freshly populated table image (copied out of HBM now), after
         # the GPU's timed region so that its threads never compete with the GPU run's host thread;
         # a second image runs the reference's shipped configuration (retry, no skew flags) beside it
@@ -227,8 +286,8 @@ def main():
     else:
         machines = 8 if cfg5 else 3
         rnd = Round(kvs, a.workers, L.membership(machines, 0), list(range(1, machines)), z, a.write_permille,
-                    a.rmw_permille, seed=a.seed,
-                    max_steps=total_steps + 2, retry_stalled=retry, fit_ack_stride=not a.no_fit_acks,
+                    a.rmw_permille, seed=a.seed, max_steps=min(total_steps + 2, REMOTE_ROUNDS),
+                    retry_stalled=retry, fit_ack_stride=not a.no_fit_acks,
                     val_credits=a.val_credits, hades=cfg5, coalesce_hot=a.coalesce_hot,
                     fused_refill=False if a.inplace_refill else None)
     torch.cuda.synchronize()
@@ -262,18 +321,25 @@ def main():
     committed = int((c1[0] - c0[0]).item())
     writes = int((c1[2] - c0[2]).item())
     dropped = int((c1[3] - c0[3]).item())
-    # probe steps (untimed): elements each batch launch applies and every launch's duration
-    rnd.count_elems = True
-    e0, inv0 = rnd.elem_totals.clone(), rnd.inv_total.clone()
+    bufs = getattr(rnd, "r", rnd)   # the replica's buffers (N>1: inside the group driver)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, bufs, kvs, a.keys, a.seed, f"_rank{rank}" if world > 1 else "")
     probe_events: dict = {}
-    for _ in range(PROBE_STEPS):
-        rnd.step(probe_events)
-    torch.cuda.synchronize()
-    n_inv, n_ack, n_val = ((rnd.elem_totals - e0).double() / PROBE_STEPS).tolist()
-    puts_per_step = float((rnd.inv_total - inv0).item()) / PROBE_STEPS
-    # how the committed ops completed (value-less GETs, coalesced PUTs: DESIGN.md section 5), over
-    # untimed rounds that continue the timed ones
-    audit = rnd.audit_rounds(AUDIT_STEPS) if world == 1 and not a.coalesce_hot else None
+    n_inv = n_ack = n_val = audit = None
+    if a.full:
+        # probe steps (untimed): elements each batch launch applies and every launch's duration
+        rnd.count_elems = True
+        e0, inv0 = rnd.elem_totals.clone(), rnd.inv_total.clone()
+        for _ in range(PROBE_STEPS):
+            rnd.step(probe_events)
+        torch.cuda.synchronize()
+        n_inv, n_ack, n_val = ((rnd.elem_totals - e0).double() / PROBE_STEPS).tolist()
+        puts_per_step = float((rnd.inv_total - inv0).item()) / PROBE_STEPS
+        # how the committed ops completed (value-less GETs, coalesced PUTs: DESIGN.md section 5), over
+        # untimed rounds that continue the timed ones
+        audit = rnd.audit_rounds(AUDIT_STEPS) if world == 1 and not a.coalesce_hot else None
+    else:   # a plain run: the INVs the last timed step sent (one per PUT that succeeded)
+        puts_per_step = float(bufs.inv_count.sum().item())
     flags = kvs.take_error_flags()
 
     convergence = None
@@ -281,7 +347,7 @@ def main():
         # every replica's table after the last round (no write in flight): the live replicas must
         # agree on every key's state, timestamp and value, and every key must be VALID again (cfg5:
         # INVALID only where the failed replica's last writes were never validated)
-        digest, not_valid = table_digest(kvs, a.keys)
+        digest, not_valid = table_digest(kvs, a.keys) if a.full else (0, 0)
         tt = torch.tensor([committed, elapsed * 1e9, flags, not_valid], dtype=torch.float64, device="cuda")
         allc = [torch.zeros_like(tt) for _ in range(world)]
         dist.all_gather(allc, tt)
@@ -292,8 +358,9 @@ def main():
         elapsed_max = max(x[1].item() for x in allc) / 1e9
         flags_any = int(max(x[2].item() for x in allc))
         live = [r for r in range(world) if not (cfg5 and r == drop_id)]
-        convergence = {"digests": [int(x.item()) for x in alld], "not_valid": [int(x[3].item()) for x in allc],
-                       "live_ranks_agree": len({int(alld[r].item()) for r in live}) == 1}
+        if a.full:
+            convergence = {"digests": [int(x.item()) for x in alld], "not_valid": [int(x[3].item()) for x in allc],
+                           "live_ranks_agree": len({int(alld[r].item()) for r in live}) == 1}
     else:
         committed_all, elapsed_max, flags_any = committed, elapsed, flags
 
@@ -305,12 +372,9 @@ def main():
     ms = dict(probe_ms)
     ms.update({k: avg(v) for k, v in events.items()})
     W, S = a.workers, Round.LOCAL
-    per_launch_bytes = {
-        "local": W * S * BYTES["get"] + puts_per_step * (BYTES["put"] - BYTES["get"]),
-        "invs": n_inv * BYTES["inv"],
-        "acks": n_ack * BYTES["ack"],
-        "vals": n_val * BYTES["val"],
-    }
+    per_launch_bytes = {"local": W * S * BYTES["get"] + puts_per_step * (BYTES["put"] - BYTES["get"])}
+    if a.full:
+        per_launch_bytes.update(invs=n_inv * BYTES["inv"], acks=n_ack * BYTES["ack"], vals=n_val * BYTES["val"])
     units = {"local": W * S, "invs": n_inv, "acks": n_ack, "vals": n_val}
     launches = {}
     for k, b in per_launch_bytes.items():
@@ -364,6 +428,7 @@ def main():
         "n_gpus": world,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": a.full,
         "ms_per_step": step_ms,
         "higher_is_better": True,
         "scaling": "weak",
@@ -397,7 +462,6 @@ def main():
             # VAL credits per worker and round (null: never binding, hermes_worker.c:479's gate idle)
             "val_credits": getattr(rnd, "V", None),
             "remote_invs_per_worker": rnd.rstride, "parallelism": f"replicas{world}",
-            "elements_per_step": {"inv": n_inv, "ack": n_ack, "val": n_val},
         },
         "roofline": {
             "bound": "hbm", "kernel": (f"{dom} batch launch (" + ("k_local_pre + k_local_fused + k_local_deferred + k_commit_w, the direct path" if dom == "local"
@@ -410,11 +474,6 @@ def main():
             "launch_samples": len(events.get(dom, [])),
             "algorithmic_bytes_per_launch": per_launch_bytes[dom],
             "launches": launches,
-            # all four batch launches' algorithmic bytes over the whole step's wall time (refill,
-            # marshalling and host synchronisation included)
-            "step": {"algorithmic_bytes": step_bytes, "ms": step_ms,
-                     "achieved": step_bytes / (step_ms / 1e3) / 1e9,
-                     "frac": step_bytes / (step_ms / 1e3) / 1e9 / HBM_PEAK_GBS},
         },
         "detail": {
             "committed_per_step_rank0": committed / a.steps, "writes_completed_rank0": writes,
@@ -426,6 +485,13 @@ def main():
             "round_stats_rank0": rnd.stats(),
         },
     }
+    if a.full:   # (the probe steps count the elements of every launch)
+        out["config"]["elements_per_step"] = {"inv": n_inv, "ack": n_ack, "val": n_val}
+        # all four batch launches' algorithmic bytes over the whole step's wall time (refill,
+        # marshalling and host synchronisation included)
+        out["roofline"]["step"] = {"algorithmic_bytes": step_bytes, "ms": step_ms,
+                                   "achieved": step_bytes / (step_ms / 1e3) / 1e9,
+                                   "frac": step_bytes / (step_ms / 1e3) / 1e9 / HBM_PEAK_GBS}
     if cfg3 and refill == "retry":
         # rounds 50-60 of configs[2] under retry: almost every slot is an RMW parked on a few thousand hot
         # keys, whose entry lines the launch finds on-die, so achieved / peak is no fraction of HBM bandwidth
@@ -471,7 +537,7 @@ def main():
                                                            "probe_ops_per_s_by_threads")}}
     if cpu is not None:
         out["cpu_baseline"] = cpu
-    if world == 1 and a.policy_steps > 0 and not cfg5:
+    if a.full and world == 1 and a.policy_steps > 0 and not cfg5:
         # the policies start from the table this run leaves: every write of it must have completed,
         # which holds only when no INV was held back by the send credits (nothing else is in flight)
         assert int(rnd.held.item()) == 0, "INVs held back: writes in flight would skew the other policies"

@@ -363,7 +363,7 @@ def test_bench_multi_rank_over_gloo(world, config):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"),
-           "--gpus", str(world), "--steps", "4", "--warmup", "1", "--keys", "30000", "--workers", "48",
+           "--gpus", str(world), "--full", "--steps", "4", "--warmup", "1", "--keys", "30000", "--workers", "48",
            "--config", config, "--dist-backend", "gloo", "--cpu-seconds", "0", "--host-api-seconds", "0"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=root)

@@ -2,6 +2,7 @@
 # One GPU call: parity tests, then (only if they pass) bench runs, optionally a rocprofv3 stats run.
 #   tools/gpu_check.sh TAG "bench args" [profile]
 tag=$1; bargs=$2; prof=$3
+bargs="--full $bargs"   # the whole bench line: CPU baselines, every launch, the other policies
 out=gpurun_out/$tag; mkdir -p $out; export TMPDIR=/tmp
 timeout -k 10 600 python -m pytest tests -m gpu -q -rf -x > $out/tests.log 2>&1; rc=$?
 echo "tests rc=$rc" >> $out/tests.log
