@@ -111,6 +111,8 @@ struct BatchArgs {
     int32_t check_unique;        // HKV_CHECK_UNIQUE: HKV_BATCH_UNIQUE launches verify their keys are unique
     uint8_t *ack_out;            // INV launches: each element's ACK (hkv_batch_desc.d_ack_out), or NULL
     uint32_t ack_out_size;
+    uint8_t *line;               // the inline residency (128 B per bucket), read and written by the <.., IL = true>
+                                 // instances only; NULL for every other launch
 };
 
 // Rounds after round 0 per batch type: how often a hot key usually mutates in one launch beyond
@@ -267,6 +269,23 @@ __device__ __forceinline__ void note_state(const BatchArgs &a, int64_t i, const 
 
 __device__ __forceinline__ uint64_t phys_of(const BatchArgs &a, uint32_t e) { return (uint64_t)e * a.g.entry_unit; }
 __device__ __forceinline__ uint8_t *entry_of(const BatchArgs &a, uint32_t e) { return a.log + phys_of(a, e); }
+// Inline instances (IL): an entry id of the local launch's scratch carries "this key's entry lives in its
+// bucket's line" in bit 31 (ids stay below it while log_cap <= kInlineMaxLog). A key's identity -- F/X/Y/T
+// words, phys_of, fw_index -- stays its log offset; only the bytes' home differs, and that is a function of the
+// bucket, so of the key, which every element, entry image and shadow holds.
+constexpr uint32_t kEntInline = 0x80000000u;
+__device__ __forceinline__ uint8_t *line_entry(const BatchArgs &a, uint64_t key)
+{
+    return a.line + ((key & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 128u + 64u;
+}
+template <bool IL>
+__device__ __forceinline__ uint32_t ent_id(uint32_t e) { return IL ? e & ~kEntInline : e; }
+template <bool IL>
+__device__ __forceinline__ uint8_t *entry_home(const BatchArgs &a, uint32_t e, uint64_t key)
+{
+    if (IL && (e & kEntInline)) return line_entry(a, key);
+    return entry_of(a, ent_id<IL>(e));
+}
 // Live entries never overlap and are at least 64 B long, so their first 64-B lines are distinct.
 // The F word of line l sits at l * odd mod 2^k (a bijection on the log's 2^k lines): keys that are
 // neighbours in the log -- the hottest ids of a populated table are -- get F words on different
@@ -493,15 +512,28 @@ constexpr int kLookupPair = 2;
 // lane), the reference's slot order (first tag match, hermesKV.c:954-975), the log window
 // (:969-970), then each lane's 16 B of the 64-B log line (bytes 16q..16q+15). All four lanes of a
 // group call it with the same arguments.
-template <int P = kLookupPair>
-__device__ __forceinline__ void lookup_pair(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
-                                            int gbase, bool *ok, uint64_t *phys, uint4 *ln)
+// IL (the inline instances, a.line set): the bucket is the first half of its 128-B line and each lane loads its
+// 16 B of the second half -- the inline key's entry -- in the same step; a hit on the flagged slot takes those
+// bytes, any other hit loads the log line as before. home: where the hit's entry bytes live (writes go there);
+// inl: the hit is its bucket's inline key. phys stays the log offset either way (the key's identity).
+template <int P = kLookupPair, bool IL = false, bool F = false>
+__device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
+                                            int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv,
+                                            uint8_t **home, bool *inl)
 {
-    uint4 v[P];
+    uint4 v[P], ev[P];
 #pragma unroll
-    for (int k = 0; k < P; ++k)
-        v[k] = probe[k] ? reinterpret_cast<const uint4 *>(a.index + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u)[q]
-                        : make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < P; ++k) {
+        if (IL) {
+            const uint4 *l = reinterpret_cast<const uint4 *>(a.line + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 128u);
+            v[k] = probe[k] ? l[q] : make_uint4(0u, 0u, 0u, 0u);
+            ev[k] = probe[k] ? l[4 + q] : make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            v[k] = probe[k] ? reinterpret_cast<const uint4 *>(a.index + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u)[q]
+                            : make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    bool il[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         const uint64_t s0 = (uint64_t)v[k].x | ((uint64_t)v[k].y << 32);
@@ -515,52 +547,52 @@ __device__ __forceinline__ void lookup_pair(const BatchArgs &a, const uint64_t *
 #pragma unroll
         for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
         const int first = o ? __ffs(o) - 1 : 0;
-        const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+        uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+        il[k] = false;
+        if (IL) {
+            il[k] = (off & kInlineOffBit) != 0;
+            off &= ~kInlineOffBit;
+        }
         ok[k] = probe[k] && o && a.g.log_head - off < a.g.log_cap;
         phys[k] = off & a.g.log_mask;
+        if (IL) il[k] = il[k] && ok[k];
     }
 #pragma unroll
-    for (int k = 0; k < P; ++k)
-        ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
+    for (int k = 0; k < P; ++k) {
+        if (IL) {
+            ln[k] = ev[k];
+            if (!il[k]) ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
+            if (home) home[k] = il[k] ? line_entry(a, key[k]) : a.log + phys[k];
+            if (inl) inl[k] = il[k];
+        } else {
+            ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
+            if (home) home[k] = a.log + phys[k];
+            if (inl) inl[k] = false;
+        }
+        if (F) fwv[k] = ok[k] && q == 0 ? a.fw[fw_index(a, phys[k])] : ~0ull;
+    }
+}
+
+template <int P = kLookupPair, bool IL = false>
+__device__ __forceinline__ void lookup_pair(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
+                                            int gbase, bool *ok, uint64_t *phys, uint4 *ln, uint8_t **home = nullptr,
+                                            bool *inl = nullptr)
+{
+    lookup_core<P, IL, false>(a, key, probe, q, gbase, ok, phys, ln, nullptr, home, inl);
 }
 
 // lookup_pair that also loads each hit's F word beside its log line (lane q == 0; ~0 for a miss), so a
 // key's F costs no dependent load after the line (k_local_fused)
-template <int P>
+template <int P, bool IL = false>
 __device__ __forceinline__ void lookup_pair_f(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
-                                              int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv)
+                                              int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv,
+                                              uint8_t **home = nullptr, bool *inl = nullptr)
 {
-    uint4 v[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k)
-        v[k] = probe[k] ? reinterpret_cast<const uint4 *>(a.index + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u)[q]
-                        : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        const uint64_t s0 = (uint64_t)v[k].x | ((uint64_t)v[k].y << 32);
-        const uint64_t s1 = (uint64_t)v[k].z | ((uint64_t)v[k].w << 32);
-        const uint32_t tag = (uint32_t)(key[k] >> 48);
-        const bool mt0 = probe[k] && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
-        const bool mt1 = probe[k] && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
-        const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu;
-        const uint32_t g1 = (uint32_t)(__ballot(mt1) >> gbase) & 0xFu;
-        uint32_t o = 0;
-#pragma unroll
-        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
-        const int first = o ? __ffs(o) - 1 : 0;
-        const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
-        ok[k] = probe[k] && o && a.g.log_head - off < a.g.log_cap;
-        phys[k] = off & a.g.log_mask;
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
-        fwv[k] = ok[k] && q == 0 ? a.fw[fw_index(a, phys[k])] : ~0ull;
-    }
+    lookup_core<P, IL, true>(a, key, probe, q, gbase, ok, phys, ln, fwv, home, inl);
 }
 
 
-template <int P = kLookupPair>
+template <int P = kLookupPair, bool IL = false>
 __global__ __launch_bounds__(256) void k_lookup(BatchArgs a, int64_t i_begin, int64_t i_end)
 {
     const int q = threadIdx.x & 3;
@@ -630,12 +662,13 @@ __global__ __launch_bounds__(256) void k_lookup(BatchArgs a, int64_t i_begin, in
     uint64_t phys[P], ekey[P];
     Meta m0[P];
     U64x2 ln[P];
+    uint8_t *home[P];
     {
         bool pr[P];
         uint4 l4[P];
 #pragma unroll
         for (int k = 0; k < P; ++k) pr[k] = probe[k] != 0;
-        lookup_pair<P>(a, key, pr, q, gbase, ok, phys, l4);
+        lookup_pair<P, IL>(a, key, pr, q, gbase, ok, phys, l4, home);
 #pragma unroll
         for (int k = 0; k < P; ++k)
             ln[k] = U64x2{(uint64_t)l4[k].x | ((uint64_t)l4[k].y << 32), (uint64_t)l4[k].z | ((uint64_t)l4[k].w << 32)};
@@ -660,7 +693,7 @@ __global__ __launch_bounds__(256) void k_lookup(BatchArgs a, int64_t i_begin, in
         uint8_t ifl = 0;
         if (ok[k] && ekey[k] == key[k]) {
             e = (uint32_t)(phys[k] / a.g.entry_unit);
-            uint8_t *entry = a.log + phys[k];
+            uint8_t *entry = IL ? home[k] : a.log + phys[k];
             if (vals_direct) {
                 const uint64_t its = pack_ts((uint32_t)(hdr[k] >> 32), (uint8_t)(hdr[k] >> 24));
                 if (its == pack_ts(m0[k].ver, m_cid(m0[k])) && m_state(m0[k]) != kValid) entry[kEntryMetaOff] = kValid;
@@ -1662,7 +1695,7 @@ constexpr int kPrePair = HKV_PRE_PAIR;   // keys per lane group in flight in the
 #else
 #define HKV_PRE_SGPR_ATTR
 #endif
-template <int HEAD = kPreHead>
+template <int HEAD = kPreHead, bool IL = false>
 __global__ __launch_bounds__(kPreThreads) HKV_PRE_ATTR HKV_PRE_SGPR_ATTR void k_local_pre(BatchArgs a)
 {
     __shared__ uint64_t hk[kPreHash], gk[kPreHash];  // the block's PUT keys, the head's
@@ -1792,7 +1825,7 @@ __global__ __launch_bounds__(kPreThreads) HKV_PRE_ATTR HKV_PRE_SGPR_ATTR void k_
                 }
             }
         }
-        lookup_pair<kPrePair>(a, key, probe, q, gbase, ok, phys, ln);
+        lookup_pair<kPrePair, IL>(a, key, probe, q, gbase, ok, phys, ln);
 #pragma unroll
         for (int k = 0; k < kPrePair; ++k) {
             Meta m0;
@@ -1872,7 +1905,7 @@ __device__ __forceinline__ void local_resolve_nm(const BatchArgs &a, uint8_t *x,
 #define HKV_LF_WAVES 2
 #endif
 constexpr int kLfWaves = HKV_LF_WAVES;   // waves per k_local_fused block (a build macro for A/B)
-template <int P, int NW>
+template <int P, int NW, bool IL = false>
 __global__ __launch_bounds__(64 * NW) HKV_LOCAL_SGPR_ATTR void k_local_fused(BatchArgs a)
 {
     constexpr int E = 16 * P;   // elements per wave: P per lane group
@@ -1928,12 +1961,13 @@ __global__ __launch_bounds__(64 * NW) HKV_LOCAL_SGPR_ATTR void k_local_fused(Bat
             probe[k] = in_count(a, (uint32_t)(i0 + te[k])) && !skip_elem_os(kLocal, (uint8_t)h0, (uint8_t)(h0 >> 8));
     }
     unsigned long long fwv[P];   // a hit's F word, loaded beside its log line
+    bool inl[P];                 // (IL) the hit is its bucket's inline key
     if (HKV_DBG_ON(a, 512)) {   // (timing modes) no F loads
-        lookup_pair<P>(a, key, probe, q, gbase, ok, phys, ln);
+        lookup_pair<P, IL>(a, key, probe, q, gbase, ok, phys, ln, nullptr, inl);
 #pragma unroll
         for (int k = 0; k < P; ++k) fwv[k] = ~0ull;
     } else {
-        lookup_pair_f<P>(a, key, probe, q, gbase, ok, phys, ln, fwv);
+        lookup_pair_f<P, IL>(a, key, probe, q, gbase, ok, phys, ln, fwv, nullptr, inl);
     }
 #pragma unroll
     for (int k = 0; k < P; ++k) {
@@ -1945,7 +1979,7 @@ __global__ __launch_bounds__(64 * NW) HKV_LOCAL_SGPR_ATTR void k_local_fused(Bat
         if (hit) sln[te[k] * 4 + q] = ln[k];
         if (q == 0) {
             sfw[te[k]] = f;
-            sent[te[k]] = hit ? (uint32_t)(phys[k] / a.g.entry_unit) : kNone;
+            sent[te[k]] = hit ? (uint32_t)(phys[k] / a.g.entry_unit) | (IL && inl[k] ? kEntInline : 0u) : kNone;
             sprb[te[k]] = probe[k];
         }
     }
@@ -1964,9 +1998,10 @@ __global__ __launch_bounds__(64 * NW) HKV_LOCAL_SGPR_ATTR void k_local_fused(Bat
             if (m_state(m) == kInvalid) {
                 // GET replays may mutate: they offer F now, and the key's elements resolve later
                 if (wm) {
-                    const uint64_t ph = phys_of(a, e);
+                    const uint64_t ph = phys_of(a, ent_id<IL>(e));
                     offer(a.fw + fw_index(a, ph), a.rtag0, (uint32_t)i);
-                    if ((uint8_t)(m.w5 >> 16) != a.ltag) a.log[ph + kEntryMetaOff + 4] = a.ltag;
+                    if ((uint8_t)(m.w5 >> 16) != a.ltag)
+                        entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(x))[kEntryMetaOff + 4] = a.ltag;
                 }
                 st = kStDefer;
                 sdef[atomicAdd(&ndef, 1u)] = (uint32_t)i;
@@ -2122,7 +2157,7 @@ __device__ __forceinline__ bool chunk_equal(const uint4 &a, const uint4 &b)
     return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
 }
 
-template <int TYPE, int P = kLookupPair>
+template <int TYPE, int P = kLookupPair, bool IL = false>
 __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 {
     constexpr int E = 16 * P;   // elements per wave: P per lane group
@@ -2162,7 +2197,8 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
             }
         }
     }
-    lookup_pair<P>(a, key, probe, q, gbase, ok, phys, ln);
+    uint8_t *home[P];   // (IL) where each hit's entry bytes live
+    lookup_pair<P, IL>(a, key, probe, q, gbase, ok, phys, ln, home);
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         Meta m;
@@ -2239,7 +2275,7 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
         }
         if (ok[k] && q > 0) {   // bytes 0..15 of a log line (the MICA key) never change
             const uint4 l = sln[te[k] * 4 + q];
-            if (!chunk_equal(l, ln[k])) reinterpret_cast<uint4 *>(a.log + phys[k])[q] = l;
+            if (!chunk_equal(l, ln[k])) reinterpret_cast<uint4 *>(IL ? home[k] : a.log + phys[k])[q] = l;
         }
     }
 }
@@ -2255,7 +2291,7 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 #else
 #define HKV_ROWS_SGPR_ATTR
 #endif
-template <int TYPE, int RMAX, int CH, int P = kLookupPair>
+template <int TYPE, int RMAX, int CH, int P = kLookupPair, bool IL = false>
 #ifdef HKV_ROWS_WAVES   // (A/B builds) waves per SIMD k_unique_rows is compiled for
 #define HKV_ROWS_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(HKV_ROWS_WAVES, 8)))
 #else
@@ -2314,7 +2350,8 @@ __global__ __launch_bounds__(64) HKV_ROWS_SGPR_ATTR HKV_ROWS_WAVES_ATTR void k_u
         part[k] = mismatch ? 0u : p;
         probe[k] = part[k] != 0;
     }
-    lookup_pair<P>(a, key, probe, q, gbase, ok, phys, ln);
+    uint8_t *home[P];   // (IL) where each hit's entry bytes live
+    lookup_pair<P, IL>(a, key, probe, q, gbase, ok, phys, ln, home);
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         Meta m;
@@ -2387,7 +2424,7 @@ __global__ __launch_bounds__(64) HKV_ROWS_SGPR_ATTR HKV_ROWS_WAVES_ATTR void k_u
         }
         if (ok[k] && q > 0) {   // bytes 0..15 of a log line (the MICA key) never change
             const uint4 l = sln[te[k] * 4 + q];
-            if (!chunk_equal(l, ln[k])) reinterpret_cast<uint4 *>(a.log + phys[k])[q] = l;
+            if (!chunk_equal(l, ln[k])) reinterpret_cast<uint4 *>(IL ? home[k] : a.log + phys[k])[q] = l;
         }
     }
 }
@@ -2526,6 +2563,7 @@ __global__ __launch_bounds__(64) void k_unique_big(BatchArgs a)
 }
 
 // Elements of keys that were INVALID at S_0, against their key's final F (k_resolve0_direct's rules)
+template <bool IL = false>
 __global__ __launch_bounds__(256) void k_local_deferred(BatchArgs a)
 {
     const uint32_t nd = a.ctr[kCtrDefer];
@@ -2536,21 +2574,23 @@ __global__ __launch_bounds__(256) void k_local_deferred(BatchArgs a)
         uint8_t idx;
         Ctx c = make_ctx(a);
         elem_at(a, i, xg, idx, c);
+        // (IL) k_local_fused wrote the op back whole, its patch applied: the key is the element's
+        uint8_t *entry = IL ? entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(xg)) : entry_of(a, e);
         Meta m;
-        meta_load(entry_of(a, e), m);
-        const uint32_t f = first_cand(*fw_of(a, e), a.rtag0);
+        meta_load(entry, m);
+        const uint32_t f = first_cand(*fw_of(a, ent_id<IL>(e)), a.rtag0);
         uint8_t st = kStDone;
         if (f == kNone || i < f) {
             Meta tm = m;
-            dispatch<31>(kLocal, xg, entry_of(a, e), idx, tm, c);
+            dispatch<31>(kLocal, xg, entry, idx, tm, c);
             if (a.error_flags && !meta_equal(tm, m)) atomicOr(a.error_flags, 1u);
         } else if (i == f) {
-            apply_to_shadow<kLocal, 31>(a, nullptr, i, entry_of(a, e));
+            apply_to_shadow<kLocal, 31>(a, nullptr, i, entry);
             st = kStCommit;
         } else {
             const Meta m1 = after_first<kLocal>(a, m, f, 0);
             Meta tm = m1;
-            dispatch<31>(kLocal, xg, entry_of(a, e), idx, tm, c);
+            dispatch<31>(kLocal, xg, entry, idx, tm, c);
             if (a.error_flags && !meta_equal(tm, m1)) atomicOr(a.error_flags, 1u);
         }
         a.st[i] = st;
@@ -2651,6 +2691,7 @@ __global__ __launch_bounds__(256) void k_commit(BatchArgs a)
 // entries at a time, four lanes per entry. One wave per 1024 elements instead of one thread per
 // element: k_commit's cost was its 4M threads, not its copies.
 constexpr int kCwElems = 1024;
+template <bool IL = false>
 __global__ __launch_bounds__(256) void k_commit_w(BatchArgs a)
 {
     __shared__ uint32_t lst[4][kCwElems];
@@ -2681,7 +2722,12 @@ __global__ __launch_bounds__(256) void k_commit_w(BatchArgs a)
     for (uint32_t j = (uint32_t)(lane >> 2); j < total; j += 16) {
         const uint32_t i = lst[w][j];
         const uint4 v = reinterpret_cast<const uint4 *>(shadow_of(a, i))[q];
-        reinterpret_cast<uint4 *>(entry_of(a, a.ent[i]))[q] = v;
+        if (IL) {   // the shadow is an entry image: its key (bytes 8..15, lane 0's) names the bucket
+            const uint64_t key = (uint64_t)(uint32_t)__shfl((int)v.z, 0, 4) | ((uint64_t)(uint32_t)__shfl((int)v.w, 0, 4) << 32);
+            reinterpret_cast<uint4 *>(entry_home<IL>(a, a.ent[i], key))[q] = v;
+        } else {
+            reinterpret_cast<uint4 *>(entry_of(a, a.ent[i]))[q] = v;
+        }
     }
 }
 
@@ -3746,6 +3792,53 @@ __global__ void k_node_suspected(const uint8_t *elems, const int32_t *ns_idx, in
     if (i >= 0) out[b] = elems[(base + i) * esz + kOpValueOff];
 }
 
+// ------------------------------------------------------------------ the inline residency's conversions
+// Four lanes per bucket, 16 B each (two slots). The inline key is the one in the bucket's lowest in-use slot:
+// chosen from the bucket alone, so the same key whenever the conversion runs (nothing is inserted under the
+// rounds). to_inline copies the bucket into the first half of its line with that slot flagged and the key's
+// whole 64-B entry into the second half; to_log copies the second half back to the entry's log offset. An
+// empty bucket's line holds the (empty) bucket and no flag; its second half is never read.
+template <bool TO_INLINE>
+__global__ __launch_bounds__(256) void k_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line,
+                                                        uint64_t num_bkts, uint64_t log_mask)
+{
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    const uint64_t b = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+    const bool live = b < num_bkts;   // (the four lanes of a group share b: a group is live or idle as a whole)
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (live) v = reinterpret_cast<const uint4 *>(index + b * 64u)[q];
+    const uint64_t s0 = (uint64_t)v.x | ((uint64_t)v.y << 32), s1 = (uint64_t)v.z | ((uint64_t)v.w << 32);
+    const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
+    const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
+    uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
+#pragma unroll
+    for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+    const int first = o ? __ffs(o) - 1 : 0;
+    const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+    if (!live) return;
+    uint4 *ln = reinterpret_cast<uint4 *>(line + b * 128u);
+    uint4 *ent = reinterpret_cast<uint4 *>(log + (off & log_mask));
+    if (TO_INLINE) {
+        if (o && (first >> 1) == q) {
+            if (first & 1) v.w |= (uint32_t)(kInlineSlotBit >> 32);
+            else v.y |= (uint32_t)(kInlineSlotBit >> 32);
+        }
+        ln[q] = v;
+        ln[4 + q] = o ? ent[q] : make_uint4(0u, 0u, 0u, 0u);
+    } else if (o) {
+        ent[q] = ln[4 + q];
+    }
+}
+
+int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uint64_t num_bkts, uint64_t log_mask,
+                          bool to_inline, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((num_bkts + 63) / 64);
+    if (to_inline) hipLaunchKernelGGL(k_layout_convert<true>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
+    else hipLaunchKernelGGL(k_layout_convert<false>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 // ------------------------------------------------------------------ host side
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -3780,10 +3873,43 @@ size_t batch_fw_words(uint64_t log_cap) { return (size_t)(log_cap >> 6); }
 
 uint32_t batch_max_epoch() { return (1u << 29) - 1; }
 
+// The paths of launch_batch, decided in one place: launch_batch takes them, and batch_inline_capable tells the
+// runtime which of them have inline instances (the kernels a configs[1] round runs).
+struct BatchPath {
+    bool small, local_direct, rows, unique_lds64, vals;
+};
+static BatchPath batch_path(const BatchLaunch &bl)
+{
+    BatchPath p{};
+    const int64_t n = bl.n;
+    p.small = (bl.path == kPathSmall || (bl.path == kPathAuto && n <= kSmallMaxElems)) && n <= kSmallMaxElems;
+    // local batches without RMWs in the default layout: the direct path (k_local_pre, k_local_fused)
+    p.local_direct = bl.type == kLocal && !bl.g.rmw_enabled && bl.esz == 56 && bl.g.st_value == 31 &&
+                     bl.g.entry_size == 64 && !bl.offsets;
+    const bool uniq = bl.unique && (bl.type == kInvs || bl.type == kAcks);
+    p.rows = bl.n_rows > 0 && bl.unique;
+    p.unique_lds64 = uniq && bl.g.st_value == 31 && bl.g.entry_size == 64 && bl.esz <= 64;
+    p.vals = bl.type == kVals;
+    return p;
+}
+
+bool batch_inline_capable(const BatchLaunch &bl)
+{
+    if (bl.n <= 0 || bl.g.entry_size != 64 || bl.g.st_value != 31) return false;
+    const BatchPath p = batch_path(bl);
+    if (p.small) return false;
+    if (p.local_direct) return true;
+    if (bl.type == kLocal || bl.type == kLocalAfterMemb) return false;
+    if (p.rows) return bl.n_rows <= 8;   // (k_unique_rows: 64-B entries and elements, checked by the runtime)
+    if (bl.unique && (bl.type == kInvs || bl.type == kAcks)) return p.unique_lds64;
+    return p.vals;
+}
+
 int launch_batch(BatchLaunch &bl, hipStream_t s)
 {
     const int64_t n = bl.n;
     if (n <= 0) return 0;
+    if (bl.line && !batch_inline_capable(bl)) return -1;
     BatchArgs a;
     a.elems = bl.elems;
     a.counts = bl.counts;
@@ -3810,6 +3936,7 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
     a.check_unique = check_unique_env;
     a.index = bl.index;
     a.log = bl.log;
+    a.line = bl.line;
     a.rw = bl.rw;
     a.ns_idx = bl.ns_idx;
     a.fw = bl.fw;
@@ -3855,11 +3982,12 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
     const bool big_direct = bl.type != kInvs;
     const unsigned rgrid = (unsigned)(big ? (n + 127) / 128 : grid);
     const size_t rlds = (size_t)(big ? 128 : 256) * (size_t)bl.esz;
-    const bool small = (bl.path == kPathSmall || (bl.path == kPathAuto && n <= kSmallMax)) && n <= kSmallMax;
+    const BatchPath bp = batch_path(bl);
+    const bool small = bp.small;
     if (bl.region_bytes && !small) return -1;  // host-staged launches are small ones
-    // local batches without RMWs in the default layout: the direct path (k_local_pre, k_local_fused)
-    const bool local_direct = bl.type == kLocal && !bl.g.rmw_enabled && bl.esz == 56 && bl.g.st_value == 31 &&
-                              bl.g.entry_size == 64 && !bl.offsets;
+    const bool local_direct = bp.local_direct;
+    const bool il = bl.line != nullptr;   // the inline instances (separate ones: a runtime branch in k_local_fused
+                                          // cost a wave of occupancy)
     // big local launches on the rounds engine (configs[2]): k_lookup reads the patches, k_resolve0_direct writes
     // the patched ops (patch_in_resolve, see there): values of at most 320 bytes, the op's pad after its value
     // within its last 8-byte word
@@ -3879,29 +4007,37 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
         if (launch_small(a, s)) return -3;
         return 0;                              // node_suspected written by the kernel
     } else if (local_direct) {
-        hipLaunchKernelGGL(k_local_pre<kPreHead>, dim3((unsigned)((n + kPreElems - 1) / kPreElems)), dim3(kPreThreads),
-                           0, s, a);
-        hipLaunchKernelGGL((k_local_fused<2, kLfWaves>), dim3((unsigned)((n + 32 * kLfWaves - 1) / (32 * kLfWaves))),
-                           dim3(64 * kLfWaves), 0, s, a);
+        const dim3 pgrid((unsigned)((n + kPreElems - 1) / kPreElems));
+        const dim3 fgrid((unsigned)((n + 32 * kLfWaves - 1) / (32 * kLfWaves)));
+        if (il) {
+            hipLaunchKernelGGL((k_local_pre<kPreHead, true>), pgrid, dim3(kPreThreads), 0, s, a);
+            hipLaunchKernelGGL((k_local_fused<2, kLfWaves, true>), fgrid, dim3(64 * kLfWaves), 0, s, a);
+            hipLaunchKernelGGL(k_local_deferred<true>, dim3(128u), dim3(256), 0, s, a);
+            hipLaunchKernelGGL(k_commit_w<true>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
+            return hipGetLastError() == hipSuccess ? 0 : -3;
+        }
+        hipLaunchKernelGGL(k_local_pre<kPreHead>, pgrid, dim3(kPreThreads), 0, s, a);
+        hipLaunchKernelGGL((k_local_fused<2, kLfWaves>), fgrid, dim3(64 * kLfWaves), 0, s, a);
         // the waiting elements' count is on the device: enough workgroups for the rounds after a
         // membership change (configs[4]: ~100 K elements of keys a failed peer left INVALID), which
         // return at once when there are few
-        hipLaunchKernelGGL(k_local_deferred, dim3(128u), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_commit_w, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_local_deferred<false>, dim3(128u), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_commit_w<false>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
     } else if (bl.n_rows > 0 && bl.unique) {  // HKV_BATCH_ROWS: one pass over positions of all rows
         // two positions per lane group, 32 per wave
         const unsigned lgrid = (unsigned)((n + kLfElems - 1) / kLfElems);
         // elements of 16 B (ACKs without RMWs) keep one chunk each in LDS, others four
-        if (bl.type == kInvs) {
-            if (bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<kInvs, 2, 4>), dim3(lgrid), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((k_unique_rows<kInvs, 8, 4>), dim3(lgrid), dim3(64), 0, s, a);
-        } else if (bl.esz <= 16) {
-            if (bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<kAcks, 2, 1>), dim3(lgrid), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((k_unique_rows<kAcks, 8, 1>), dim3(lgrid), dim3(64), 0, s, a);
-        } else {
-            if (bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<kAcks, 2, 4>), dim3(lgrid), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((k_unique_rows<kAcks, 8, 4>), dim3(lgrid), dim3(64), 0, s, a);
-        }
+#define HKV_ROWS(T, CH)                                                                                           \
+    do {                                                                                                         \
+        if (il && bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, kLookupPair, true>), dim3(lgrid), dim3(64), 0, s, a); \
+        else if (il) hipLaunchKernelGGL((k_unique_rows<T, 8, CH, kLookupPair, true>), dim3(lgrid), dim3(64), 0, s, a); \
+        else if (bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH>), dim3(lgrid), dim3(64), 0, s, a);  \
+        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH>), dim3(lgrid), dim3(64), 0, s, a);                      \
+    } while (0)
+        if (bl.type == kInvs) HKV_ROWS(kInvs, 4);
+        else if (bl.esz <= 16) HKV_ROWS(kAcks, 1);
+        else HKV_ROWS(kAcks, 4);
+#undef HKV_ROWS
     } else if (bl.unique && (bl.type == kInvs || bl.type == kAcks)) {  // one pass: every key has one element
         // in-place unique pass (big-entry ACKs, other geometries): one element per lane group
         const unsigned ugrid1 = (unsigned)((n + 63) / 64);
@@ -3918,7 +4054,9 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
             // 64-B entries: the LDS-staged pass, one element per lane group (16 per wave). Same box, INV phase
             // per step (gpurun_out/r04m, r04t): 72-77 us at 1 element per lane group, 78-80 at 2, 91 at 4
             const unsigned g1 = (unsigned)((n + 15) / 16);
-            if (bl.type == kInvs) hipLaunchKernelGGL((k_unique_lds<kInvs, 1>), dim3(g1), dim3(64), 0, s, a);
+            if (il && bl.type == kInvs) hipLaunchKernelGGL((k_unique_lds<kInvs, 1, true>), dim3(g1), dim3(64), 0, s, a);
+            else if (il) hipLaunchKernelGGL((k_unique_lds<kAcks, 1, true>), dim3(g1), dim3(64), 0, s, a);
+            else if (bl.type == kInvs) hipLaunchKernelGGL((k_unique_lds<kInvs, 1>), dim3(g1), dim3(64), 0, s, a);
             else hipLaunchKernelGGL((k_unique_lds<kAcks, 1>), dim3(g1), dim3(64), 0, s, a);
         } else if (lds_big) {
             // big-object INVs, whose raises copy 287-B values: staged through LDS (cfg3: 460 -> 326 us per
@@ -3930,7 +4068,8 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
     } else if (bl.type == kVals) {             // one pass (see k_lookup)
         // one element per lane group. Same box, VAL batch per step (gpurun_out/r04m, r04u): 49.6-50.2 us at 1,
         // 52.3-53.9 at 2, 57 at 4
-        hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, n);
+        if (il) hipLaunchKernelGGL((k_lookup<1, true>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, n);
+        else hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, n);
         return hipGetLastError() == hipSuccess ? 0 : -3;
     } else {
     // The head split pays off where one launch piles many candidates onto a few keys: local

@@ -21,6 +21,8 @@ struct BatchLaunch {
     uint8_t *rw_state;           // ACK launches: state-byte mirror of read_write_ops (may be NULL)
     const uint8_t *index;
     uint8_t *log;
+    uint8_t *line;               // the table's inline residency (hkv_runtime.hip "layouts"), or NULL: the launch
+                                 // runs on index and log. Set only for launches batch_inline_capable() accepts
     uint8_t *rw;
     int64_t rw_stride;
     int32_t *ns_idx;
@@ -162,11 +164,32 @@ struct TableView {
     Geometry g;
     const uint8_t *index;
     const uint8_t *log;
+    const uint8_t *line;   // non-NULL: the table is INLINE and the kernel reads the inline keys' entries there
 };
-int table_view(const hkv_table *t, TableView *out);
+// What a consumer of the view does with the table, which decides the layout it is given (hkv_runtime.hip
+// "layouts"): kViewLog -- it reads index and log as they are (the table is converted to LOG first, on
+// stream); kViewLive -- its kernels know the inline residency (the table goes to its preferred layout, as
+// before an inline-capable batch launch); kViewStatic -- it reads only what never changes under the rounds
+// (geometry, buckets, the keys of entries): no conversion.
+enum : int32_t { kViewLog = 0, kViewLive = 1, kViewStatic = 2 };
+int table_view(hkv_table *t, TableView *out, hipStream_t stream, int32_t mode);
 
-int launch_batch(BatchLaunch &bl, hipStream_t s);
+// The private inline residency: one 128-B line per bucket -- the bucket, then the whole entry of
+// the key in its lowest in-use slot, whose slot carries kInlineSlotBit. A located offset (k_peer_locate) and
+// an entry id of a local launch's scratch carry the same fact in a spare bit.
+constexpr uint64_t kInlineSlotBit = 1ull << 63;   // bit 39 of a slot's 40-bit offset field
+constexpr uint64_t kInlineOffBit = 1ull << 39;    // ... as seen in the offset (slot >> 24)
+constexpr uint64_t kInlineMaxLog = 1ull << 36;    // log_cap of an eligible table: offsets stay below bit 39,
+                                                  // entry ids below bit 31
+constexpr uint64_t kPhysInline = 1ull << 62;      // hkv_wl_peer_locate's offsets (~0: a miss)
+// index + log -> lines (to_inline), or the inline entries back to their log offsets
+int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uint64_t num_bkts, uint64_t log_mask,
+                          bool to_inline, hipStream_t s);
+// whether launch_batch runs this launch on kernels that know the inline residency (bl.line aside)
+bool batch_inline_capable(const BatchLaunch &bl);
+
 constexpr int64_t kSmallMaxElems = 4096;   // launches the single-workgroup kernel can take
+int launch_batch(BatchLaunch &bl, hipStream_t s);
 int launch_populate(const PopulateLaunch &pl, hipStream_t s);
 int launch_hash_ids(const uint32_t *ids, uint64_t *out, int64_t n, hipStream_t s);
 size_t sort_temp_bytes(int64_t n, int key_bits);

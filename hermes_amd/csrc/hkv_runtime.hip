@@ -129,6 +129,12 @@ struct hkv_table {
     hipStream_t stream = nullptr;
     uint8_t *d_index = nullptr;
     uint8_t *d_log = nullptr;
+    // layouts (see "layouts" below): the inline residency, 128 B per bucket, allocated by the first
+    // hkv_table_prefer_layout(INLINE) of an eligible table
+    uint8_t *d_line = nullptr;
+    int layout_pref = HKV_LAYOUT_LOG, layout_state = HKV_LAYOUT_LOG;
+    uint64_t conversions = 0, inline_launches = 0;
+    hipStream_t last_stream = nullptr;   // the stream of the table's last launch or conversion
     unsigned long long *d_evictions = nullptr;
     int64_t inserted = 0;
     uint32_t skip_key = 0;
@@ -316,13 +322,70 @@ static void plan_log(uint64_t h0, uint64_t cap, uint32_t e, uint32_t maxv, uint6
     final_head = (n < k) ? h0 + n * e : hw + (n - k) * e;
 }
 
+// ---- layouts. A table is LOG (d_index / d_log are the truth: the reference's image) or INLINE (d_line is the
+// truth for every bucket's inline key, whose log entry is stale; every other entry lives in the log as before;
+// d_index never changes). All residency rules are here: before a launch whose kernels know the lines the table
+// goes to its preferred layout, before anything else that reads or writes the image it goes to LOG. Kernels
+// without an inline instance therefore need no change.
+static bool layout_eligible(const hkv_table *t)
+{
+    return t->geo.entry_size == 64 && !t->cfg.big_objects && t->geo.log_head <= t->geo.log_cap &&
+           t->geo.log_cap <= kInlineMaxLog;
+}
+
+// Conversions run in stream order on `s`. A launch on another stream than the table's last one is ordered by
+// the caller (hermeskv.h: one stream at a time per table); the conversion in front of it waits for that stream
+// itself, since the caller does not know it is there.
+static int layout_set(hkv_table *t, int want, hipStream_t s)
+{
+    if (t->layout_state == want) {
+        t->last_stream = s;
+        return 0;
+    }
+    if (t->last_stream != s) HIP_TRY(hipStreamSynchronize(t->last_stream));
+    if (launch_layout_convert(t->d_index, t->d_log, t->d_line, t->cfg.num_bkts, t->geo.log_mask,
+                              want == HKV_LAYOUT_INLINE, s))
+        return fail(-3, "layout conversion launch failed: %s", hipGetErrorString(hipGetLastError()));
+    TRACE("layout -> %s", want == HKV_LAYOUT_INLINE ? "INLINE" : "LOG");
+    t->layout_state = want;
+    t->last_stream = s;
+    ++t->conversions;
+    return 0;
+}
+
+// before a launch: capable = its kernels know the lines. Returns the line array the launch runs on, or NULL.
+static int layout_for_launch(hkv_table *t, bool capable, hipStream_t s, uint8_t **line)
+{
+    const bool inl = capable && t->layout_pref == HKV_LAYOUT_INLINE && t->d_line && layout_eligible(t);
+    if (int rc = layout_set(t, inl ? HKV_LAYOUT_INLINE : HKV_LAYOUT_LOG, s)) return rc;
+    if (inl) ++t->inline_launches;
+    *line = inl ? t->d_line : nullptr;
+    return 0;
+}
+
+// before an export or anything else outside the launches: the reference's image, complete, and the device idle
+// on it. (The null stream does not order the table's non-blocking streams.)
+static int layout_export(hkv_table *t)
+{
+    if (t->layout_state == HKV_LAYOUT_LOG) return 0;
+    hipStream_t s = t->last_stream;
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (int rc = layout_set(t, HKV_LAYOUT_LOG, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
 namespace hkv {
-int table_view(const hkv_table *t, TableView *out)
+int table_view(hkv_table *t, TableView *out, hipStream_t stream, int32_t mode)
 {
     if (!t || !out) return -1;
+    uint8_t *line = nullptr;
+    if (mode != kViewStatic && layout_for_launch(t, mode == kViewLive, stream, &line)) return -1;
     out->g = t->geo;
     out->index = t->d_index;
     out->log = t->d_log;
+    out->line = line;
     return 0;
 }
 }  // namespace hkv
@@ -399,6 +462,7 @@ int hkv_table_destroy(hkv_table *t)
     if (t->stream) hipStreamSynchronize(t->stream);
     hipFree(t->d_index);
     hipFree(t->d_log);
+    hipFree(t->d_line);
     hipFree(t->d_evictions);
     hipFree(t->d_batch);
     hipFree(t->d_fw);
@@ -456,6 +520,7 @@ int hkv_table_populate(hkv_table *t, int64_t n, int val_len)
     if (n > 0x7FFFFFFFll) return fail(-1, "populate: at most 2^31-1 keys (32-bit key ids)");
     std::lock_guard<std::mutex> lk(t->mu);
     HIP_TRY(hipSetDevice(t->cfg.device));
+    if (int rc = layout_export(t)) return rc;   // inserts go into index and log
     int bbits = bit_width(t->cfg.num_bkts - 1);
     if (bbits == 0) bbits = 1;
     // populate temporaries: hashes, sort pairs and sort storage, freed before returning
@@ -636,7 +701,8 @@ int hkv_batch_async(hkv_table *t, const hkv_batch_desc *d, void *stream)
         bl.row_stride = d->row_stride;
         bl.path = kPathEngine;
     }
-    TRACE("batch_async type=%d n=%lld", d->type, (long long)n);
+    if (int lrc = layout_for_launch(t, batch_inline_capable(bl), s, &bl.line)) return lrc;
+    TRACE("batch_async type=%d n=%lld%s", d->type, (long long)n, bl.line ? " (inline)" : "");
     rc = launch_batch(bl, s);
     if (rc) return fail(rc, "batch launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
     return 0;
@@ -675,6 +741,7 @@ int hkv_copy_index(hkv_table *t, void *dst, uint64_t off, uint64_t bytes)
     if (!t || !dst) return fail(-1, "null argument");
     if (off + bytes > t->cfg.num_bkts * 64) return fail(-1, "index range out of bounds");
     srv_stop(t);
+    if (int rc = layout_export(t)) return rc;
     HIP_TRY(hipStreamSynchronize(t->stream));
     HIP_TRY(hipMemcpy(dst, t->d_index + off, bytes, hipMemcpyDeviceToHost));
     return 0;
@@ -685,6 +752,7 @@ int hkv_copy_log(hkv_table *t, void *dst, uint64_t off, uint64_t bytes)
     if (!t || !dst) return fail(-1, "null argument");
     if (off + bytes > t->cfg.log_cap + t->geo.entry_size) return fail(-1, "log range out of bounds");
     srv_stop(t);
+    if (int rc = layout_export(t)) return rc;
     HIP_TRY(hipStreamSynchronize(t->stream));
     HIP_TRY(hipMemcpy(dst, t->d_log + off, bytes, hipMemcpyDeviceToHost));
     return 0;
@@ -700,7 +768,11 @@ int64_t hkv_num_index_evictions(const hkv_table *t)
     return (int64_t)v;
 }
 
-void *hkv_device_index(hkv_table *t) { return t ? t->d_index : nullptr; }
+void *hkv_device_index(hkv_table *t)
+{
+    if (!t || layout_export(t)) return nullptr;
+    return t->d_index;
+}
 
 int hkv_take_error_flags(hkv_table *t, uint32_t *out)
 {
@@ -712,7 +784,77 @@ int hkv_take_error_flags(hkv_table *t, uint32_t *out)
     HIP_TRY(hipDeviceSynchronize());  // null-stream memset vs the non-blocking launch streams
     return 0;
 }
-void *hkv_device_log(hkv_table *t) { return t ? t->d_log : nullptr; }
+void *hkv_device_log(hkv_table *t)
+{
+    if (!t || layout_export(t)) return nullptr;
+    return t->d_log;
+}
+
+// room for the lines beside everything else, with a margin for the launches' scratch and the caller's buffers
+static bool layout_room(const hkv_table *t)
+{
+    const size_t bytes = (size_t)t->cfg.num_bkts * 128;
+    size_t free_b = 0, total_b = 0;
+    if (hipSetDevice(t->cfg.device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+    return free_b >= bytes + bytes / 4 + ((size_t)1 << 30);
+}
+
+// The lines, once allocated, stay until the table is destroyed: a table sent back to LOG keeps them for the
+// next INLINE preference (freeing 16 GiB waits for the device). Like the launches, one caller at a time per table.
+int hkv_table_prefer_layout(hkv_table *t, int layout)
+{
+    if (!t) return fail(-1, "null table");
+    if (layout != HKV_LAYOUT_LOG && layout != HKV_LAYOUT_INLINE) return fail(-1, "unknown layout %d", layout);
+    std::lock_guard<std::mutex> lk(t->mu);   // against hkv_table_populate (geo.log_head)
+    t->layout_pref = layout;
+    if (layout == HKV_LAYOUT_LOG || !layout_eligible(t)) return 0;
+    if (!t->d_line) {
+        const size_t bytes = (size_t)t->cfg.num_bkts * 128;
+        if (!layout_room(t)) return 0;
+        if (hipMalloc(&t->d_line, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            t->d_line = nullptr;
+            return 0;
+        }
+    }
+    return 1;
+}
+
+int hkv_table_layout(hkv_table *t, hkv_layout_info *out)
+{
+    if (!t || !out) return fail(-1, "null argument");
+    memset(out, 0, sizeof *out);
+    out->state = t->layout_state;
+    out->preferred = t->layout_pref;
+    // what hkv_table_prefer_layout(INLINE) would answer now: the lines are there, or there is room for them
+    out->eligible = layout_eligible(t) && (t->d_line || layout_room(t));
+    out->conversions = t->conversions;
+    out->inline_launches = t->inline_launches;
+    out->line_bytes = t->d_line ? (uint64_t)t->cfg.num_bkts * 128 : 0;
+    return 0;
+}
+
+int hkv_table_apply_layout(hkv_table *t, void *stream)
+{
+    if (!t) return fail(-1, "null table");
+    srv_stop(t);
+    uint8_t *line;
+    if (int rc = layout_for_launch(t, true, (hipStream_t)stream, &line)) return rc;
+    if (line) --t->inline_launches;   // (no launch ran)
+    return 0;
+}
+
+int hkv_copy_lines(hkv_table *t, void *dst, uint64_t off, uint64_t bytes)
+{
+    if (!t || !dst) return fail(-1, "null argument");
+    if (!t->d_line) return fail(-1, "the inline residency is not allocated");
+    if (off + bytes > t->cfg.num_bkts * 128) return fail(-1, "line range out of bounds");
+    srv_stop(t);
+    HIP_TRY(hipStreamSynchronize(t->stream));
+    HIP_TRY(hipStreamSynchronize(t->last_stream));
+    HIP_TRY(hipMemcpy(dst, t->d_line + off, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 int hkv_hash_ids(const uint32_t *d_ids, uint64_t *d_keys_second, int64_t n, void *stream)
 {
@@ -887,6 +1029,7 @@ static void host_launch_mixed(hkv_table *t, HostSet *set, std::unique_lock<std::
     }
     BatchLaunch bl;
     memset(&bl, 0, sizeof bl);
+    if (layout_export(t)) die("hermes_batch_ops_to_KVS (layout)");   // the host entry point's kernels read index and log
     bl.g = t->geo;
     bl.index = t->d_index;
     bl.log = t->d_log;
@@ -988,6 +1131,7 @@ static void srv_ensure(hkv_table *t)
         std::lock_guard<std::mutex> tl(t->mu);   // against hkv_table_populate (geo.log_head)
         sl.c.g = t->geo;
     }
+    if (layout_export(t)) die("hermes_batch_ops_to_KVS (layout)");
     sl.c.index = t->d_index;
     sl.c.log = t->d_log;
     sl.c.error_flags = t->d_error_flags;
@@ -1125,6 +1269,7 @@ static void host_launch_part(hkv_table *t, std::unique_lock<std::mutex> &lk)
         h.w_ack_init = (uint8_t)(r->mb >> 16);
         for (int g = 0; g <= kPartG; ++g) pl.part[g][b] = r->poff[g];
     }
+    if (layout_export(t)) die("hermes_batch_ops_to_KVS (layout)");
     pl.c.index = t->d_index;
     pl.c.log = t->d_log;
     pl.c.error_flags = t->d_error_flags;

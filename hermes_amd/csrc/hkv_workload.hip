@@ -1362,20 +1362,35 @@ __global__ __launch_bounds__(256) void k_peer_compact(const uint32_t *ids, const
 
 // the MICA lookup of hermesKV.c:952-993 (first tag match, wrap test, 8-B key compare): the
 // entry's physical offset, or ~0 for a miss
+// FLAG: with kPhysInline set where the match is the bucket's lowest in-use slot: that key is the bucket's inline key
+// whenever the table is INLINE (hkv_internal.h), a fact of the index alone. The key compare reads entry bytes
+// 8..15, which never change, so the log serves it in either layout.
+template <bool FLAG = false>
 __device__ __forceinline__ uint64_t find_entry(const TableView &t, uint64_t key)
 {
     const uint64_t *b = reinterpret_cast<const uint64_t *>(t.index + ((key & 0xFFFFFFFFFFFFULL) & t.g.bkt_mask) * 64u);
     const uint32_t tag = (uint32_t)(key >> 48);
+    bool lowest = true;
     for (int s = 0; s < 8; ++s) {
         const uint64_t slot = b[s];
         if ((slot & 1u) && ((uint32_t)(slot >> 1) & 0x7FFFFFu) == tag) {
             const uint64_t off = slot >> 24;
             if (t.g.log_head - off >= t.g.log_cap) return ~0ull;
             const uint64_t phys = off & t.g.log_mask;
-            return *reinterpret_cast<const uint64_t *>(t.log + phys + 8) == key ? phys : ~0ull;
+            if (*reinterpret_cast<const uint64_t *>(t.log + phys + 8) != key) return ~0ull;
+            return phys | (FLAG && lowest && t.g.log_cap <= kInlineMaxLog ? kPhysInline : 0ull);
         }
+        if (slot & 1u) lowest = false;
     }
     return ~0ull;
+}
+
+// where a located entry's bytes live: IL instances run on an INLINE table (t.line set)
+template <bool IL>
+__device__ __forceinline__ const uint8_t *located_entry(const TableView &t, uint64_t loc, uint64_t key)
+{
+    if (IL && (loc & kPhysInline)) return t.line + ((key & 0xFFFFFFFFFFFFULL) & t.g.bkt_mask) * 128u + 64u;
+    return t.log + (loc & ~kPhysInline);
 }
 
 // The virtual peers' per-entry words: live entries never overlap and are entry_size long, so
@@ -1709,7 +1724,7 @@ __global__ __launch_bounds__(256) void k_peer_locate(TableView t, const uint8_t 
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (g >= total) return;
-    phys_out[g] = find_entry(t, *reinterpret_cast<const uint64_t *>(invs + g * op_size));
+    phys_out[g] = find_entry<true>(t, *reinterpret_cast<const uint64_t *>(invs + g * op_size));
 }
 
 // k_peer_ts for located INVs (one thread each): the key is checked at the entry, and an INV
@@ -1723,6 +1738,7 @@ struct PeerTsArgs {   // hkv_wl_peer_ts_at's arguments
     unsigned long long *peer_ts;
     uint32_t round;
 };
+template <bool IL>
 __device__ __forceinline__ void peer_ts_at_body(const PeerTsArgs &pt, int bx)
 {
     const TableView &t = pt.t;
@@ -1745,7 +1761,7 @@ __device__ __forceinline__ void peer_ts_at_body(const PeerTsArgs &pt, int bx)
     uint32_t cur = 0;
     bool ok = false;
     if (phys != ~0ull) {
-        const U64x2w *e = reinterpret_cast<const U64x2w *>(t.log + phys);
+        const U64x2w *e = reinterpret_cast<const U64x2w *>(located_entry<IL>(t, phys, key));
         const U64x2w l0 = e[0], l1 = e[1];  // key at 8, timestamp version at 24
         if (l0.b == key) {
             ok = true;
@@ -1753,12 +1769,13 @@ __device__ __forceinline__ void peer_ts_at_body(const PeerTsArgs &pt, int bx)
         }
     }
     if (!ok) {
-        phys = find_entry(t, key);
+        phys = find_entry<true>(t, key);
         if (phys != ~0ull) {
             ok = true;
-            cur = *reinterpret_cast<const uint32_t *>(t.log + phys + 24);
+            cur = *reinterpret_cast<const uint32_t *>(located_entry<IL>(t, phys, key) + 24);
         }
     }
+    phys &= ~kPhysInline;   // (a miss is not used below)
     uint32_t ver = 2;
     if (ok) {
         ver = cur + ((!t.g.rmw_enabled || rmw) ? 2u : 4u);
@@ -1773,16 +1790,18 @@ __device__ __forceinline__ void peer_ts_at_body(const PeerTsArgs &pt, int bx)
     *reinterpret_cast<uint64_t *>(vv + 8) = (vh & 0xFFFFFF00ull & 0xFFFFFFFFull) | kOpVal | ((uint64_t)ver << 32);
 }
 
-__global__ __launch_bounds__(256) void k_peer_ts_at(PeerTsArgs pt) { peer_ts_at_body(pt, blockIdx.x); }
+template <bool IL>
+__global__ __launch_bounds__(256) void k_peer_ts_at(PeerTsArgs pt) { peer_ts_at_body<IL>(pt, blockIdx.x); }
 
 // The refill plan of this round and the virtual peers' timestamps of the next, in one launch (round 6): both
 // run between a round's VAL batch and the next local launch, touch disjoint data (op mirrors and patches; the
 // peers' slabs, reading the table) and are bound by dependent loads, so side by side in one grid they overlap
 // and the launch boundary between them goes. Blocks [0, plan_blocks) plan, the rest take timestamps.
+template <bool IL>
 __global__ __launch_bounds__(256) HKV_PLAN_SGPR_ATTR void k_plan_peer_ts(PlanArgs pa, PeerTsArgs pt, int plan_blocks)
 {
     if ((int)blockIdx.x < plan_blocks) refill_plan_body<2>(pa, blockIdx.x);
-    else peer_ts_at_body(pt, (int)blockIdx.x - plan_blocks);
+    else peer_ts_at_body<IL>(pt, (int)blockIdx.x - plan_blocks);
 }
 
 }  // namespace hkv
@@ -1909,8 +1928,8 @@ int hkv_wl_peer_acks_pm(hkv_table *t, const uint8_t *inv_out, const int32_t *inv
 {
     if (n_peers <= 0 || n_workers <= 0 || ack_size < kOpMetaSize || ack_size % 8 || !inv_off) return -1;
     if (max_invs <= 0 || max_invs > inv_stride) return -1;
-    TableView tv{};
-    if (peer_ts && table_view(t, &tv)) return -1;
+    TableView tv{};   // peer_answer reads buckets and entries' keys only (find_entry): either layout serves
+    if (peer_ts && table_view(t, &tv, (hipStream_t)stream, kViewStatic)) return -1;
     const int32_t out_stride = max_invs * n_peers;
     int64_t total = (int64_t)n_workers * out_stride;
     hipLaunchKernelGGL(k_peer_acks, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, inv_out, inv_count,
@@ -1926,8 +1945,8 @@ int hkv_wl_peer_acks(hkv_table *t, const uint8_t *inv_out, const int32_t *inv_co
 {
     if (n_peers <= 0 || n_workers <= 0 || ack_size < kOpMetaSize || ack_size % 8) return -1;
     if (out_stride % n_peers || out_stride > inv_stride * n_peers || out_stride <= 0) return -1;
-    TableView tv{};
-    if (peer_ts && table_view(t, &tv)) return -1;
+    TableView tv{};   // (find_entry only, as above)
+    if (peer_ts && table_view(t, &tv, (hipStream_t)stream, kViewStatic)) return -1;
     int64_t total = (int64_t)n_workers * out_stride;
     hipLaunchKernelGGL(k_peer_acks, dim3(blocks_for(total)), dim3(256), 0, (hipStream_t)stream, inv_out, inv_count,
                        inv_stride, op_size, acks, ack_size, out_stride, ack_count, peer_ids, n_peers, total, tv,
@@ -1982,7 +2001,7 @@ int hkv_wl_peer_ts(hkv_table *t, uint8_t *invs, uint8_t *vals, const int32_t *co
                    int32_t stride, uint32_t op_size, unsigned long long *peer_ts, uint32_t round, void *stream)
 {
     TableView tv;
-    if (table_view(t, &tv) || n_workers <= 0 || stride <= 0 || op_size % 8) return -1;
+    if (table_view(t, &tv, (hipStream_t)stream, kViewLog) || n_workers <= 0 || stride <= 0 || op_size % 8) return -1;
     const int64_t total = (int64_t)n_workers * stride;
     const int64_t per_block = 64 * kPeerTsPair;  // 4 lanes per element, kPeerTsPair elements per group
     hipLaunchKernelGGL(k_peer_ts, dim3((unsigned)((total + per_block - 1) / per_block)), dim3(256), 0,
@@ -1993,7 +2012,7 @@ int hkv_wl_peer_ts(hkv_table *t, uint8_t *invs, uint8_t *vals, const int32_t *co
 uint64_t hkv_wl_peer_ts_words(const hkv_table *t)
 {
     TableView tv;
-    if (table_view(t, &tv)) return 0;
+    if (table_view(const_cast<hkv_table *>(t), &tv, nullptr, kViewStatic)) return 0;
     return (tv.g.log_cap / tv.g.entry_size + 1) * 8;
 }
 
@@ -2173,8 +2192,8 @@ int hkv_wl_peer_acks_queue(hkv_table *t, const uint8_t *inv_out, const int32_t *
                            const unsigned long long *peer_ts, uint32_t round, void *stream)
 {
     if (n_peers <= 0 || n_workers <= 0 || ack_size < kOpMetaSize || ack_size % 8 || q_stride <= 0) return -1;
-    TableView tv{};
-    if (peer_ts && table_view(t, &tv)) return -1;
+    TableView tv{};   // (find_entry only, as hkv_wl_peer_acks_pm)
+    if (peer_ts && table_view(t, &tv, (hipStream_t)stream, kViewStatic)) return -1;
     hipLaunchKernelGGL(k_peer_acks_q, dim3(n_workers), dim3(256), 0, (hipStream_t)stream, inv_out, inv_count, inv_stride,
                        op_size, aq, ack_size, q_stride, aq_n, vq_n, acnt, peer_ids, n_peers, tv, peer_ts, round);
     return ok();
@@ -2197,8 +2216,8 @@ extern "C" {
 
 int hkv_wl_peer_locate(hkv_table *t, const uint8_t *invs, int64_t n, uint32_t op_size, uint64_t *phys_out, void *stream)
 {
-    TableView tv;
-    if (table_view(t, &tv) || n < 0 || op_size % 8) return -1;
+    TableView tv;   // buckets and entries' keys only: either layout serves (find_entry)
+    if (table_view(t, &tv, (hipStream_t)stream, kViewStatic) || n < 0 || op_size % 8) return -1;
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_peer_locate, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, tv, invs, op_size, n,
                        phys_out);
@@ -2209,10 +2228,12 @@ int hkv_wl_peer_ts_at(hkv_table *t, uint8_t *invs, uint8_t *vals, const uint64_t
                       unsigned long long *peer_ts, uint32_t round, void *stream)
 {
     TableView tv;
-    if (table_view(t, &tv) || n < 0 || op_size % 8) return -1;
+    if (n < 0 || op_size % 8) return -1;
     if (n == 0) return 0;
+    if (table_view(t, &tv, (hipStream_t)stream, kViewLive)) return -1;
     const PeerTsArgs pt{tv, invs, vals, phys, n, op_size, peer_ts, round};
-    hipLaunchKernelGGL(k_peer_ts_at, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
+    if (tv.line) hipLaunchKernelGGL(k_peer_ts_at<true>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
+    else hipLaunchKernelGGL(k_peer_ts_at<false>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
     return ok();
 }
 
@@ -2226,17 +2247,24 @@ int hkv_wl_refill_plan_peer_ts(uint8_t *states, int32_t n_workers, int32_t strid
     if (flags & ~(uint32_t)(HKV_WL_REFILL_ALL | HKV_WL_READ_TS_RESET)) return -1;
     if (((uintptr_t)patch & 15) || (st_value >> shift) > 255) return -1;
     TableView tv;
-    if (table_view(t, &tv) || n < 0 || op_size % 8) return -1;
+    if (n < 0 || op_size % 8) return -1;
+    // (without INVs the kernel does not read the table: no conversion for it)
+    if (table_view(t, &tv, (hipStream_t)stream, n ? kViewLive : kViewStatic)) return -1;
     const PlanArgs pa{states, n_workers, stride, st_value, shift, tkey, top, tlen, cursor, machine_id, flags, counters, opc,
                       patch};
     const PeerTsArgs pt{tv, invs, vals, phys, n, op_size, peer_ts, round};
     const int plan_blocks = (n_workers + 7) / 8;
 #ifdef HKV_PLAN_PTS_SPLIT   // (a build macro for A/B: the two launches of before)
     hipLaunchKernelGGL(k_refill_plan_w<2>, dim3((unsigned)plan_blocks), dim3(256), 0, (hipStream_t)stream, pa);
-    if (n) hipLaunchKernelGGL(k_peer_ts_at, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
+    if (n && tv.line) hipLaunchKernelGGL(k_peer_ts_at<true>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
+    else if (n) hipLaunchKernelGGL(k_peer_ts_at<false>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
 #else
-    hipLaunchKernelGGL(k_plan_peer_ts, dim3((unsigned)plan_blocks + blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pa,
-                       pt, plan_blocks);
+    if (tv.line)
+        hipLaunchKernelGGL(k_plan_peer_ts<true>, dim3((unsigned)plan_blocks + blocks_for(n)), dim3(256), 0,
+                           (hipStream_t)stream, pa, pt, plan_blocks);
+    else
+        hipLaunchKernelGGL(k_plan_peer_ts<false>, dim3((unsigned)plan_blocks + blocks_for(n)), dim3(256), 0,
+                           (hipStream_t)stream, pa, pt, plan_blocks);
 #endif
     return ok();
 }

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .lib import ABI_VERSION, HkvBatchDesc, HkvConfig, Membership, check, raw
+from .lib import ABI_VERSION, HkvBatchDesc, HkvConfig, HkvLayoutInfo, Membership, check, raw
 
 _L = raw()
 
@@ -81,6 +81,9 @@ def sized_geometry(num_keys: int, sizes: L.Sizes = L.DEFAULT) -> tuple[int, int]
     cap = 1 << max(16, (need - 1).bit_length())
     return min(bkts, 1 << (27 if num_keys <= 1 << 28 else 29)), cap
 
+
+LAYOUT_LOG = 0      # hkv_table_prefer_layout (include/hermeskv.h, "Table layouts")
+LAYOUT_INLINE = 1   # a private 128-B line per bucket: the bucket and its first key's entry
 
 BATCH_ENGINE = 1   # hkv_batch_desc.flags (include/hermeskv.h): the multi-kernel engine
 BATCH_SMALL = 2    # the single-workgroup kernel (launches of at most 4096 elements)
@@ -334,6 +337,33 @@ class HermesKV:
         if off is None:
             return None
         return self.log_bytes(off, self.sizes.entry).view(L.entry_dtype(self.sizes))[0]
+
+    # -- layouts (include/hermeskv.h, "Table layouts")
+    def prefer_layout(self, layout: int) -> bool:
+        """hkv_table_prefer_layout: the sticky preference; whether the table is eligible for it"""
+        rc = _L.hkv_table_prefer_layout(self.h, int(layout))
+        if rc < 0:
+            check(rc, "hkv_table_prefer_layout")
+        return rc == 1
+
+    def layout(self) -> dict:
+        """state, preference, eligibility and the counters (conversions, launches run while INLINE)"""
+        v = HkvLayoutInfo()
+        check(_L.hkv_table_layout(self.h, ctypes.byref(v)), "hkv_table_layout")
+        return {"state": v.state, "preferred": v.preferred, "eligible": bool(v.eligible), "conversions": v.conversions,
+                "inline_launches": v.inline_launches, "line_bytes": v.line_bytes}
+
+    def apply_layout(self, stream: torch.cuda.Stream | None = None) -> None:
+        """convert to the preferred layout now, as the next inline-capable launch would"""
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_apply_layout(self.h, ctypes.c_void_p(s)), "hkv_table_apply_layout")
+
+    def line_bytes(self, offset: int = 0, nbytes: int | None = None) -> np.ndarray:
+        """debug export of the inline residency (128 B per bucket, private format)"""
+        nbytes = self.cfg.num_bkts * 128 - offset if nbytes is None else nbytes
+        out = np.empty(nbytes, dtype=np.uint8)
+        check(_L.hkv_copy_lines(self.h, out.ctypes.data_as(ctypes.c_void_p), offset, nbytes), "hkv_copy_lines")
+        return out
 
     def device_index(self) -> int:
         return _L.hkv_device_index(self.h)

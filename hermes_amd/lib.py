@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 HERE = os.path.dirname(os.path.abspath(__file__))
 # HKV_LIB: another build of the same library (A/B timing of two revisions in one GPU session)
 LIB_PATH = os.environ.get("HKV_LIB") or os.path.join(HERE, "libhermeskv.so")
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)")
@@ -42,6 +42,12 @@ class HkvBatchDesc(ctypes.Structure):
                 ("d_put_keys", ctypes.c_void_p), ("n_rows", ctypes.c_int32), ("skip_row", ctypes.c_int32),
                 ("row_stride", ctypes.c_int64), ("d_ack_out", ctypes.c_void_p), ("ack_out_size", ctypes.c_uint32),
                 ("d_phys", ctypes.c_void_p)]
+
+
+class HkvLayoutInfo(ctypes.Structure):
+    _fields_ = [("state", ctypes.c_int32), ("preferred", ctypes.c_int32), ("eligible", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("conversions", ctypes.c_uint64), ("inline_launches", ctypes.c_uint64),
+                ("line_bytes", ctypes.c_uint64)]
 
 
 class Membership(ctypes.Structure):
@@ -73,6 +79,10 @@ _L.hkv_device_index.argtypes = [_P]
 _L.hkv_take_error_flags.argtypes = [_P, ctypes.POINTER(ctypes.c_uint32)]
 _L.hkv_device_log.restype = _P
 _L.hkv_device_log.argtypes = [_P]
+_L.hkv_table_prefer_layout.argtypes = [_P, ctypes.c_int]
+_L.hkv_table_layout.argtypes = [_P, ctypes.POINTER(HkvLayoutInfo)]
+_L.hkv_table_apply_layout.argtypes = [_P, _P]
+_L.hkv_copy_lines.argtypes = [_P, _P, ctypes.c_uint64, ctypes.c_uint64]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

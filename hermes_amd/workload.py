@@ -11,12 +11,13 @@ from __future__ import annotations
 
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
 
 from . import layout as L
-from .kvs import HermesKV
+from .kvs import LAYOUT_INLINE, HermesKV
 from .lib import check, raw
 
 _L = raw()
@@ -365,6 +366,19 @@ class Round:
         # instead of a marshal pass over the applied INVs
         self.fused_acks = (self.pack_remote and ((kvs.sizes.entry == 64 and self.op <= 64) or
                                                  (kvs.sizes.entry == 320 and self.op <= 320)))
+        # Where every launch of a round knows the table's inline residency (include/hermeskv.h, "Table layouts":
+        # the local direct launch, per-peer unique INV launches, the ACK rows launch, the VAL launch, the located
+        # peer timestamps), an eligible table runs the rounds on it: one 128-B line per lookup of a bucket's first
+        # key instead of two. Any other round shape would convert the table back and forth every round, so it
+        # stays in the reference layout, as does every table under HKV_INLINE=0 (A/B timing). Under VAL credits the
+        # ACKs queue per worker and go in a non-unique ACK launch (the rounds engine, which has no inline
+        # instance), so those rounds stay LOG too. Which launches are capable is decided by batch_inline_capable
+        # (hkv_batch.hip) and the table readers' view modes (hkv_workload.hip); this predicate only mirrors them,
+        # and a mismatch costs conversions, never correctness. A device_log() / device_index() pointer taken
+        # before a round is stale once the round has run on an INLINE table: take it again (the call converts).
+        all_capable = (not kvs.rmw and kvs.sizes.entry == 64 and self.op == 56 and val_credits is None and
+                       (self.R == 0 or (self.pack_remote and self.fit and self.ack_rows)))
+        self.inline = all_capable and os.environ.get("HKV_INLINE", "1") != "0" and kvs.prefer_layout(LAYOUT_INLINE)
         self.drops = []                # peers dropped from the membership (membership_change)
         self.alive = self.R            # live peers: the first `alive` slots of the remote slabs
         self._counts = {}

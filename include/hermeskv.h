@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define HKV_ABI_VERSION 8
+#define HKV_ABI_VERSION 9
 
 /* ------------------------------------------------------------------ reference types
  * Declared here only when the reference's own spacetime.h has not been included; the
@@ -252,6 +252,41 @@ void *hkv_device_index(hkv_table *t);
  *        HKV_BATCH_ROWS position's rows disagree on the key */
 int  hkv_take_error_flags(hkv_table *t, uint32_t *out);
 void *hkv_device_log(hkv_table *t);
+
+/* Table layouts (ABI 9). The table image every export above returns is the reference's: a 64-B bucket per
+ * index slot group and the log. The library may keep a second, private residency beside it, "inline": one
+ * 128-B line per bucket holding the bucket and the whole 64-B entry of the key in its lowest in-use slot, so
+ * that a lookup of that key (about 70 % of the keys at one key per bucket) reads one memory line instead of
+ * two. A table is in one of two states: LOG (index and log are the truth) or INLINE (the lines are the truth
+ * for the inline keys; their log entries are stale until the table returns to LOG). The library converts by
+ * itself: to the preferred layout before a launch whose kernels know the lines (64-B entries without RMWs:
+ * the local direct launch, unique INV / ACK launches, ACK rows launches, VAL launches), to LOG before every
+ * other launch, before a populate and before every export above (hkv_device_index / hkv_device_log wait for
+ * the table's streams first; the pointers they return are current until the next launch).
+ * hkv_table_prefer_layout sets the sticky preference and returns 1 when the table is eligible (64-B
+ * entries, a log that has not wrapped, log_cap <= 2^36, room for 128 B per bucket in device memory), 0 when
+ * it is not (the table then stays LOG), negative on error. The default preference is LOG. Once allocated, the
+ * lines stay until hkv_table_destroy, also after a preference of LOG. A pointer from hkv_device_index /
+ * hkv_device_log that is held across launches goes stale on an INLINE table (the inline keys' log entries
+ * are not updated there): call again after the launches, which converts and returns the current image. */
+#define HKV_LAYOUT_LOG 0
+#define HKV_LAYOUT_INLINE 1
+typedef struct hkv_layout_info {
+    int32_t state;               /* HKV_LAYOUT_* the table is in now */
+    int32_t preferred;           /* HKV_LAYOUT_* */
+    int32_t eligible;            /* what hkv_table_prefer_layout(t, HKV_LAYOUT_INLINE) would return now */
+    int32_t reserved;
+    uint64_t conversions;        /* conversions so far, either way */
+    uint64_t inline_launches;    /* launches (batch launches and the workload's table readers) run while INLINE */
+    uint64_t line_bytes;         /* device memory of the inline residency (0: not allocated) */
+} hkv_layout_info;
+int  hkv_table_prefer_layout(hkv_table *t, int layout);
+int  hkv_table_layout(hkv_table *t, hkv_layout_info *out);
+/* converts to the preferred layout now (as the next inline-capable launch would), on `stream` */
+int  hkv_table_apply_layout(hkv_table *t, void *stream);
+/* debug export of the inline residency (128 B per bucket, private format: bit 63 of a slot word is the inline
+ * flag), in the manner of hkv_copy_index; does not convert. An error while the residency is not allocated. */
+int  hkv_copy_lines(hkv_table *t, void *host_dst, uint64_t offset, uint64_t bytes);
 
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);

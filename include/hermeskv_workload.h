@@ -150,7 +150,10 @@ uint64_t hkv_wl_peer_ts_words(const hkv_table *t);
 /* The same for n INVs stored back to back (and their VALs), with each INV's entry located
  * beforehand: hkv_wl_peer_locate writes the log offset of every INV's key (~0 when absent) into
  * d_phys once per pre-drawn round index; hkv_wl_peer_ts_at reads one entry line per INV (an INV
- * whose entry no longer holds its key takes the full lookup). */
+ * whose entry no longer holds its key takes the full lookup). The words of d_phys are opaque to the
+ * caller: besides the offset they carry whether the key is its bucket's first one (bit 62), which tells
+ * hkv_wl_peer_ts_at where the entry lives while the table is in the inline layout (hermeskv.h, "Table
+ * layouts"); both calls and hkv_wl_refill_plan_peer_ts run on either layout without converting it. */
 int hkv_wl_peer_locate(hkv_table *t, const uint8_t *d_invs, int64_t n, uint32_t op_size, uint64_t *d_phys,
                        void *stream);
 int hkv_wl_peer_ts_at(hkv_table *t, uint8_t *d_invs, uint8_t *d_vals, const uint64_t *d_phys, int64_t n,
