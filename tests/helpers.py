@@ -122,12 +122,58 @@ def val_callbacks(acks: np.ndarray, live: np.ndarray, machine_id: int):
 class Mirror:
     """Runs every batch launch of a device table on an oracle twin and compares."""
 
-    def __init__(self, g, o, name):
+    def __init__(self, g, o, name, table_check="every", expect_inline=None):
+        """table_check "every": index and log are exported and compared after every launch. An export sends an
+        INLINE table back to LOG, and the conversion that follows copies every inline key's entry from the log
+        into its line, so each launch then starts with log and line byte-equal and a kernel that reads an inline
+        key from the wrong one of the two still answers right. "deferred": a launch compares everything but the
+        table, nothing it does converts, and check_table() compares index and log where the test says so.
+        expect_inline (may be set anew before every launch): None -- no layout check; True -- the launch ran
+        on the lines (state INLINE after it, inline_launches + 1, one conversion if the table was LOG before);
+        False -- it ran on index and log (state LOG, inline_launches unchanged, one conversion if the table
+        was INLINE before)."""
+        assert table_check in ("every", "deferred")
         self.g, self.o, self.name = g, o, name
+        self.table_check, self.expect_inline = table_check, expect_inline
         self.launches = 0
         self.codes = collections.Counter()   # (batch type, "in8"/"out8"/"out9", code) over live elements
         self._orig = g.batch
         g.batch = self.batch
+
+    def _launch(self, *a, **k):
+        """the device launch, with the layout counters around it (hkv_table_layout: does not convert)"""
+        before = self.g.layout()
+        self._orig(*a, **k)
+        after = self.g.layout()
+        what = f"{self.name} launch {self.launches}"
+        if self.expect_inline is not None:
+            inl = bool(self.expect_inline)
+            assert after["state"] == (1 if inl else 0), f"{what}: ran in layout {after['state']}: {before} -> {after}"
+            assert after["inline_launches"] == before["inline_launches"] + (1 if inl else 0), \
+                f"{what}: inline launches {before} -> {after}"
+            assert after["conversions"] == before["conversions"] + (1 if before["state"] != after["state"] else 0), \
+                f"{what}: conversions {before} -> {after}"
+        self._layout_after = after
+
+    def _table(self, what):
+        """the end of a launch's checks: the table (every launch, or left to check_table), the consistency
+        flags, and in deferred mode that nothing since the launch moved the layout"""
+        if self.table_check == "every":
+            self.check_table(what)
+        assert self.g.take_error_flags() == 0, f"{what}: device consistency flags"
+        if self.table_check == "deferred":
+            assert self.g.layout() == self._layout_after, \
+                f"{what}: a per-launch check converted the table: {self._layout_after} -> {self.g.layout()}"
+
+    def check_table(self, what):
+        """index and log against the oracle's (the exports send an INLINE table back to LOG)"""
+        self._check_log(what)
+        assert np.array_equal(self.g.index_bytes(), self.o.index_bytes()), f"{what}: index differs"
+
+    def _check_ns(self, node_suspected, ns_o, what):
+        if node_suspected is not None:
+            got = node_suspected.cpu().numpy()
+            assert np.array_equal(got, ns_o), f"{what}: node_suspected {got.tolist()} != oracle {ns_o.tolist()}"
 
     def _count(self, btype, tag, col, arr, n_batches, stride, elem_size, counts):
         v = arr.reshape(n_batches, stride, elem_size)[:, :, col]
@@ -149,11 +195,12 @@ class Mirror:
                                   rw[: nrw * self.g.sizes.op].cpu().numpy().reshape(nrw, self.g.sizes.op)[:, 8]), \
                 "read_write_ops opcode mirror is stale"
         if rows is not None:
+            assert node_suspected is None, "HKV_BATCH_ROWS takes no node_suspected"
             return self._rows(btype, elems, n_batches, stride, elem_size, membership, offsets, stream, rw,
                               rw_stride_bytes, rw_state, rows, rw_opcodes, ack_out)
         if offsets is not None:
             return self._packed(btype, elems, n_batches, stride, elem_size, membership, offsets, stream, rw,
-                                rw_stride_bytes, rw_state, unique, ack_out, ack_out_size, rw_opcodes)
+                                rw_stride_bytes, rw_state, unique, ack_out, ack_out_size, rw_opcodes, node_suspected)
         torch.cuda.synchronize()
         n = n_batches * stride * elem_size
         vt = np.dtype((np.void, elem_size))
@@ -174,13 +221,15 @@ class Mirror:
             rw_in = rw.cpu().numpy().copy().view(np.dtype((np.void, self.g.sizes.op)))
             st_before = rw_in.view(np.uint8).reshape(-1, self.g.sizes.op)[:, 9].copy()
         rws_in = rw_state.cpu().numpy().copy() if rw_state is not None else None
-        self._orig(btype, elems, n_batches, stride, elem_size, membership, counts, rw, rw_stride_bytes,
-                   node_suspected, stream, state_out=state_out, opcode_in=opcode_in, patch=patch, rw_state=rw_state,
-                   unique=unique, rw_opcodes=rw_opcodes, ack_out=ack_out, ack_out_size=ack_out_size)
+        ns_o = node_suspected.cpu().numpy().copy() if node_suspected is not None else None
+        self._launch(btype, elems, n_batches, stride, elem_size, membership, counts, rw, rw_stride_bytes,
+                     node_suspected, stream, state_out=state_out, opcode_in=opcode_in, patch=patch, rw_state=rw_state,
+                     unique=unique, rw_opcodes=rw_opcodes, ack_out=ack_out, ack_out_size=ack_out_size)
         torch.cuda.synchronize()
         self.o.batch_multi(int(btype), e_in, n_batches, stride, c_in, membership, rw_in,
-                           rw_stride_bytes // self.g.sizes.op if rw is not None else 0)
+                           rw_stride_bytes // self.g.sizes.op if rw is not None else 0, node_suspected=ns_o)
         what = f"{self.name} launch {self.launches} type {int(btype)}"
+        self._check_ns(node_suspected, ns_o, what)
         if ack_out is not None:   # the launch also ran the ACK callbacks on its applied INVs (d_ack_out)
             eo = e_in.view(np.uint8).reshape(-1, elem_size)
             j = np.arange(n_batches * stride) % stride
@@ -218,9 +267,7 @@ class Mirror:
             rw_op = rw.cpu().numpy()
             assert np.array_equal(rw_op, rw_in.view(np.uint8)), f"{what}: read_write_ops differ"
             self._check_rw_state(rw_state, rws_in, st_before, rw_op.reshape(-1, self.g.sizes.op)[:, 9], what)
-        self._check_log(what)
-        assert np.array_equal(self.g.index_bytes(), self.o.index_bytes()), f"{what}: index differs"
-        assert self.g.take_error_flags() == 0, f"{what}: device consistency flags"
+        self._table(what)
         if state_out is not None:   # the local batch's state mirror: every element's state byte
             mirror = state_out[: n_batches * stride].cpu().numpy()
             assert np.array_equal(mirror, got.reshape(-1, elem_size)[:, 9]), f"{what}: state mirror differs"
@@ -267,9 +314,9 @@ class Mirror:
                 continue
             flat = flat_all[r * row_stride * elem_size:(r * row_stride + total) * elem_size].reshape(total, elem_size)
             ins[r] = flat.copy()
-        self._orig(btype, elems, n_batches, total, elem_size, membership, rw=rw, rw_stride_bytes=rw_stride_bytes,
-                   stream=stream, offsets=offsets, rw_state=rw_state, unique=True, rows=rows, rw_opcodes=rw_opcodes,
-                   ack_out=ack_out)
+        self._launch(btype, elems, n_batches, total, elem_size, membership, rw=rw, rw_stride_bytes=rw_stride_bytes,
+                     stream=stream, offsets=offsets, rw_state=rw_state, unique=True, rows=rows, rw_opcodes=rw_opcodes,
+                     ack_out=ack_out)
         torch.cuda.synchronize()
         got_all = elems.cpu().numpy()
         vals_all = ack_out.cpu().numpy() if ack_out is not None else None
@@ -309,14 +356,12 @@ class Mirror:
             rw_op = rw.cpu().numpy()
             assert np.array_equal(rw_op, rw_in.view(np.uint8)), f"{what}: read_write_ops differ"
             self._check_rw_state(rw_state, rws_in, st_before, rw_op.reshape(-1, self.g.sizes.op)[:, 9], what)
-        self._check_log(what)
-        assert np.array_equal(self.g.index_bytes(), self.o.index_bytes()), f"{what}: index differs"
-        assert self.g.take_error_flags() == 0, f"{what}: device consistency flags"
+        self._table(what)
         self.launches += 1
 
     def _packed(self, btype, elems, n_batches, total, elem_size, membership, offsets, stream, rw=None,
                 rw_stride_bytes=0, rw_state=None, unique=False, ack_out=None, ack_out_size=16,
-                rw_opcodes=None):
+                rw_opcodes=None, node_suspected=None):
         """A packed (HKV_BATCH_PACKED) INV / ACK / VAL launch: the oracle applies the same batches
         laid out in rows; the device's packed output must equal the oracle's rows packed again."""
         import torch
@@ -333,16 +378,18 @@ class Mirror:
         rw_in = rw.cpu().numpy().copy().view(np.dtype((np.void, self.g.sizes.op))) if rw is not None else None
         st_before = rw_in.view(np.uint8).reshape(-1, self.g.sizes.op)[:, 9].copy() if rw is not None else None
         rws_in = rw_state.cpu().numpy().copy() if rw_state is not None else None
-        self._orig(btype, elems, n_batches, total, elem_size, membership, rw=rw, rw_stride_bytes=rw_stride_bytes,
-                   stream=stream, offsets=offsets, rw_state=rw_state, unique=unique, ack_out=ack_out,
-                   ack_out_size=ack_out_size, rw_opcodes=rw_opcodes)
+        ns_o = node_suspected.cpu().numpy().copy() if node_suspected is not None else None
+        self._launch(btype, elems, n_batches, total, elem_size, membership, rw=rw, rw_stride_bytes=rw_stride_bytes,
+                     node_suspected=node_suspected, stream=stream, offsets=offsets, rw_state=rw_state, unique=unique,
+                     ack_out=ack_out, ack_out_size=ack_out_size, rw_opcodes=rw_opcodes)
         torch.cuda.synchronize()
         e_in = rows.reshape(-1).view(np.dtype((np.void, elem_size))).copy()
         self.o.batch_multi(int(btype), e_in, n_batches, width, cnt, membership, rw_in,
-                           rw_stride_bytes // self.g.sizes.op if rw is not None else 0)
+                           rw_stride_bytes // self.g.sizes.op if rw is not None else 0, node_suspected=ns_o)
         want = e_in.view(np.uint8).reshape(n_batches, width, elem_size)[pos]
         got = elems[: total * elem_size].cpu().numpy().reshape(total, elem_size)
         what = f"{self.name} launch {self.launches} type {int(btype)} (packed)"
+        self._check_ns(node_suspected, ns_o, what)
         grow = np.zeros_like(rows)
         grow[pos] = got
         if ack_out is not None:   # the launch also ran the ACK callbacks on its output (d_ack_out)
@@ -368,7 +415,5 @@ class Mirror:
             rw_op = rw.cpu().numpy()
             assert np.array_equal(rw_op, rw_in.view(np.uint8)), f"{what}: read_write_ops differ"
             self._check_rw_state(rw_state, rws_in, st_before, rw_op.reshape(-1, self.g.sizes.op)[:, 9], what)
-        self._check_log(what)
-        assert np.array_equal(self.g.index_bytes(), self.o.index_bytes()), f"{what}: index differs"
-        assert self.g.take_error_flags() == 0, f"{what}: device consistency flags"
+        self._table(what)
         self.launches += 1

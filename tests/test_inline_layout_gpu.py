@@ -19,6 +19,7 @@ from hermes_amd import layout as L  # noqa: E402
 from oracle.oracle import OracleKVS  # noqa: E402
 from tests import gen  # noqa: E402
 from tests.helpers import Mirror  # noqa: E402
+from tests.inline_cases import census  # noqa: E402
 
 N_KEYS, BKTS, CAP = 4096, 4096, 1 << 19
 LOG, INLINE = 0, 1
@@ -29,19 +30,6 @@ FLAG = np.uint64(1 << 63)
 def _need_gpu():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-
-
-def census(index: np.ndarray, log: np.ndarray, cap: int):
-    """From the exported image: every bucket's slots, its lowest in-use slot (-1: empty), the inline keys
-    (the keys of the entries those slots name), and the census the base geometry promises."""
-    slots = index.view("<u8").reshape(-1, 8)
-    used = (slots & np.uint64(1)).astype(bool)
-    n_used = used.sum(axis=1)
-    first = np.where(n_used > 0, used.argmax(axis=1), -1)
-    nz = np.nonzero(first >= 0)[0]
-    phys = ((slots[nz, first[nz]] >> np.uint64(24)) & np.uint64(cap - 1)).astype(np.int64)
-    keys = log[(phys[:, None] + np.arange(8, 16)[None, :])].copy().view("<u8").reshape(-1)
-    return slots, first, nz, phys, keys, n_used
 
 
 def assert_census(n_keys, nz, n_used):
