@@ -118,6 +118,9 @@ class HermesKV:
         check(_L.hkv_table_create(ctypes.byref(self.cfg), ctypes.byref(h)), "hkv_table_create")
         self.h = h
         self._owned = True
+        # batch launches and populates through this object so far: what a caller read from the table before the
+        # count moved (Round's next-round peer timestamps) may be stale
+        self.launches = 0
         if populate and nk:
             self.populate(nk, self.sizes.kvs_value)
 
@@ -130,6 +133,7 @@ class HermesKV:
         self = cls.__new__(cls)
         self.h = ctypes.c_void_p(h)
         self._owned = False
+        self.launches = 0
         self.cfg = HkvConfig()
         check(_L.hkv_table_config(self.h, ctypes.byref(self.cfg)), "hkv_table_config")
         self.sizes = L.Sizes(bool(self.cfg.big_objects), self.cfg.extra_cache_lines if self.cfg.big_objects else 0)
@@ -157,6 +161,7 @@ class HermesKV:
         self.skew = int(skew)
 
     def populate(self, n: int, val_len: int) -> None:
+        self.launches += 1
         check(_L.hkv_table_populate(self.h, int(n), int(val_len)), "hkv_table_populate")
 
     @property
@@ -247,6 +252,7 @@ class HermesKV:
         for i, b in enumerate(membership[:8]):
             d.membership[i] = b
         s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        self.launches += 1
         check(_L.hkv_batch_async(self.h, ctypes.byref(d), ctypes.c_void_p(s)), "hkv_batch_async")
 
     def batch_host(self, btype: int, elems: np.ndarray, membership: bytes, rw: np.ndarray | None = None,

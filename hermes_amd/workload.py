@@ -387,7 +387,8 @@ class Round:
             self._hades_start()
         self._gen_remote()
         self.audit: CommitAudit | None = None   # audit_rounds(): per-outcome commit breakdown (untimed)
-        self._pts_done = None          # (clock, live peers) whose virtual-peer timestamps the last refill took
+        # (clock, live peers, the table's launch count) of the virtual-peer timestamps the last refill took
+        self._pts_done = None
         self.refill(first=True)
 
     def _gen_remote(self):
@@ -442,7 +443,9 @@ class Round:
     def refill(self, first: bool = False, next_round: bool = False):
         """refill_ops for the next round. next_round (the end of Round.step, clock already advanced): the
         plan and the next round's virtual-peer timestamps in one launch (hkv_wl_refill_plan_peer_ts), which
-        the next step then does not repeat."""
+        the next step then does not repeat -- unless the table was launched on or populated in between
+        (HermesKV.launches): then the step reads them again from the table as it is. Writes that bypass this
+        HermesKV object (the reference entry points on the default table) are not seen."""
         if self.fused and not first and next_round and self.pack_remote and self.R and self.alive:
             k = self.clock % max(len(self.remote_inv), 1)
             pi, pv, _, _, phys, _ = self.remote_packed[k]
@@ -453,7 +456,7 @@ class Round:
                                                 _ptr(self.counters), _ptr(self.opcodes), _ptr(self.patch), self.kvs.h,
                                                 _ptr(pi), _ptr(pv), _ptr(phys), total, self.op, _ptr(self.peer_ts),
                                                 self.clock, _s()), "refill_plan_peer_ts")
-            self._pts_done = (self.clock, self.alive)
+            self._pts_done = (self.clock, self.alive, self.kvs.launches)
             return
         if self.fused and not first:   # a plan the next local launch applies (the ops stay as they are)
             check(_L.hkv_wl_refill_plan(_ptr(self.states), self.W, self.LOCAL, self.sizes.st_value, self.sizes.shift,
@@ -656,7 +659,8 @@ class Round:
         # the packed slabs (same elements, same order): the live peers are their first `alive` peers (a
         # failed peer is always the last live one), so after a failure the rounds apply a prefix of them
         packed = self.pack_remote
-        pts_done, self._pts_done = self._pts_done == (self.clock, sent), None
+        # (... unless a launch or a populate on the table came between: they were read from the table as it was)
+        pts_done, self._pts_done = self._pts_done == (self.clock, sent, self.kvs.launches), None
         if self.R and sent and not pts_done:   # (the last refill may have taken them already)
             if packed:
                 self.peer_timestamps_packed(k, sent)

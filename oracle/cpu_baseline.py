@@ -10,6 +10,8 @@ from __future__ import annotations
 import ctypes
 import os
 
+import numpy as np
+
 from .oracle import Config, build, lib
 
 
@@ -33,6 +35,51 @@ def host_cores() -> dict:
     affinity set, and the usable count (host_threads: capped by OMP_NUM_THREADS, 16 on the GPU box)."""
     aff = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None
     return {"host_cpus": os.cpu_count(), "host_affinity_cpus": aff, "host_usable_threads": host_threads()}
+
+
+BENCH_TRACE_LEN, BENCH_PEER_ROUNDS = 8192, 16   # hkv_oracle_bench.c: BT, BP
+
+
+def _hz(zipf) -> HkoZipf:
+    return HkoZipf(zipf.theta, zipf.zetan, zipf.alpha, zipf.eta, zipf.half_pow, zipf.n)
+
+
+def bench_gen_trace(zipf, n_workers: int, length: int, write_permille: int, seed: int):
+    """The traces hko_bench_rounds runs on (hko_bench_gen_trace): (key, op, id) of trace[w * length + j]"""
+    build()
+    L = lib()
+    L.hko_bench_gen_trace.restype = None
+    L.hko_bench_gen_trace.argtypes = [ctypes.POINTER(HkoZipf), ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
+                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    n = n_workers * length
+    key, op, ids = np.empty(n, np.uint64), np.empty(n, np.uint8), np.empty(n, np.uint32)
+    hz = _hz(zipf)
+    L.hko_bench_gen_trace(ctypes.byref(hz), n_workers, length, write_permille, ctypes.c_uint64(seed),
+                          key.ctypes.data_as(ctypes.c_void_p), op.ctypes.data_as(ctypes.c_void_p),
+                          ids.ctypes.data_as(ctypes.c_void_p))
+    return key, op, ids
+
+
+def bench_gen_peer_rounds(zipf, n_workers: int, n_peers: int, per_peer: int, n_rounds: int, op_size: int,
+                          st_value: int, seed: int):
+    """The virtual peers' slabs hko_bench_rounds applies (hko_bench_gen_peer_rounds): INVs
+    [n_rounds][n_workers][n_peers * per_peer][op_size], VALs [..][16] (zero past a worker's count), counts
+    [n_rounds][n_workers]"""
+    build()
+    L = lib()
+    L.hko_bench_gen_peer_rounds.restype = None
+    L.hko_bench_gen_peer_rounds.argtypes = [ctypes.POINTER(HkoZipf), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    rs = n_peers * per_peer
+    invs = np.zeros((n_rounds, n_workers, rs, op_size), np.uint8)
+    vals = np.zeros((n_rounds, n_workers, rs, 16), np.uint8)
+    counts = np.zeros((n_rounds, n_workers), np.int32)
+    hz = _hz(zipf)
+    L.hko_bench_gen_peer_rounds(ctypes.byref(hz), n_workers, n_peers, per_peer, n_rounds, op_size, st_value,
+                                ctypes.c_uint64(seed), invs.ctypes.data_as(ctypes.c_void_p),
+                                vals.ctypes.data_as(ctypes.c_void_p), counts.ctypes.data_as(ctypes.c_void_p))
+    return invs, vals, counts
 
 
 class TableSnapshot:

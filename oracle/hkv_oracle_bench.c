@@ -222,6 +222,76 @@ static void *bench_worker(void *arg)
     return NULL;
 }
 
+/* The traces of the timed loop (create_uni_trace / parse_trace shape): trace[w * len + j] = key, opcode and
+ * id -- hkv_wl_gen_trace without RMWs. Exported so that a test can hold it against the generators' model. */
+void hko_bench_gen_trace(const hko_zipf *z, int n_workers, int len, uint32_t write_pm, uint64_t seed,
+                         uint64_t *tkey, uint8_t *top, uint32_t *tid)
+{
+    for (int64_t g = 0; g < (int64_t)n_workers * len; g++) {
+        uint64_t r1 = sm64(seed ^ (0x1000003ull * (uint64_t)g)), r2 = sm64(r1 ^ 0x5EEDull);
+        uint32_t id = (uint32_t)zipf_draw(z, (double)(r1 >> 11) * (1.0 / 9007199254740992.0));
+        tkey[g] = key_of(id);
+        tid[g] = id;
+        top[g] = (uint32_t)(r2 % 1000u) < write_pm ? OPC_PUT : OPC_GET;
+    }
+}
+
+/* Peer INVs + VALs, n_rounds round indices deep: per round, each virtual peer's (peer r = machine 1 + r) first
+ * write of a key (in its worker-major op order), compacted per worker in peer order -- the GPU run's
+ * hkv_wl_gen_peer_round without RMW flags. rinv_pool / rval_pool: [n_rounds][n_workers][n_peers * per_peer]
+ * elements of osz / 16 bytes, zeroed by the caller; rcount [n_rounds][n_workers]. The timestamps are taken from
+ * the table when a round uses them. */
+void hko_bench_gen_peer_rounds(const hko_zipf *z, int n_workers, int n_peers, int per_peer, int n_rounds,
+                               uint32_t osz, uint32_t sv, uint64_t seed, uint8_t *rinv_pool, uint8_t *rval_pool,
+                               int32_t *rcount)
+{
+    const int rstride = n_peers * per_peer;
+    const int64_t per_round = (int64_t)n_workers * rstride;
+    size_t hs = 1024;
+    while (hs < 2 * (size_t)(per_round ? per_round : 1)) hs <<= 1;
+    uint64_t *hk = malloc(hs * sizeof(uint64_t));
+    uint32_t *ids = malloc(sizeof(uint32_t) * (size_t)(per_round ? per_round : 1));
+    uint8_t *keep = malloc((size_t)(per_round ? per_round : 1));
+    for (int k = 0; k < n_rounds && rstride; k++) {
+        memset(hk, 0, hs * sizeof(uint64_t));
+        for (int64_t g = 0; g < per_round; g++) {
+            uint64_t r1 = sm64(seed ^ ((uint64_t)k << 40) ^ (0x9E37ull * (uint64_t)g));
+            ids[g] = (uint32_t)zipf_draw(z, (double)(r1 >> 11) * (1.0 / 9007199254740992.0));
+        }
+        /* peer-major over the worker-major draws: a (peer, id) pair's first occurrence wins */
+        for (int r = 0; r < n_peers; r++)
+            for (int w = 0; w < n_workers; w++)
+                for (int j = 0; j < per_peer; j++) {
+                    int64_t g = (int64_t)w * rstride + (int64_t)r * per_peer + j;
+                    uint64_t key = (((uint64_t)r << 32) | ids[g]) + 1;
+                    size_t h = (size_t)(sm64(key) & (hs - 1));
+                    while (hk[h] != 0 && hk[h] != key) h = (h + 1) & (hs - 1);
+                    keep[g] = hk[h] == 0;
+                    hk[h] = key;
+                }
+        for (int w = 0; w < n_workers; w++) {
+            int cnt = 0;
+            for (int r = 0; r < n_peers; r++)
+                for (int j = 0; j < per_peer; j++) {
+                    int64_t g = (int64_t)w * rstride + (int64_t)r * per_peer + j;
+                    if (!keep[g]) continue;
+                    uint8_t peer = (uint8_t)(1 + r);
+                    size_t o = ((size_t)k * n_workers + w) * rstride + cnt++;
+                    uint8_t *x = rinv_pool + o * osz, *v = rval_pool + o * 16;
+                    uint64_t key = key_of(ids[g]);
+                    memcpy(x, &key, 8);
+                    x[8] = OPC_INV; x[9] = peer; x[10] = (uint8_t)sv; x[11] = peer;
+                    memset(x + 12, 0, 6);
+                    memset(x + 18, 'a' + peer, sv);
+                    memcpy(v, x, 16);
+                    v[8] = OPC_VAL;
+                }
+            rcount[(size_t)k * n_workers + w] = cnt;
+        }
+    }
+    free(hk); free(ids); free(keep);
+}
+
 /* returns committed ops of all threads; rounds (per thread, the smallest) and seconds (the
  * slowest thread's) through out-params */
 int64_t hko_bench_rounds(hko_kvs *kv, const hko_config *cfg, int n_workers, int n_threads, double seconds,
@@ -243,64 +313,9 @@ int64_t hko_bench_rounds(hko_kvs *kv, const hko_config *cfg, int n_workers, int 
     memset(hot, 255, (size_t)n_workers * 200);
     uint32_t *cursor = calloc(n_workers, 4);
     const uint8_t mid = (uint8_t)cfg->machine_id;
-    /* traces (create_uni_trace / parse_trace shape) */
-    for (int64_t g = 0; g < (int64_t)n_workers * T; g++) {
-        uint64_t r1 = sm64(seed ^ (0x1000003ull * (uint64_t)g)), r2 = sm64(r1 ^ 0x5EEDull);
-        uint32_t id = (uint32_t)zipf_draw(z, (double)(r1 >> 11) * (1.0 / 9007199254740992.0));
-        tkey[g] = key_of(id);
-        tid[g] = id;
-        top[g] = (uint32_t)(r2 % 1000u) < write_pm ? OPC_PUT : OPC_GET;
-    }
-    /* peer INVs + VALs, P round indices deep: per round, each virtual peer's first write of a key
-     * (in its worker-major op order), compacted per worker in peer order -- the GPU run's
-     * hkv_wl_gen_peer_round. The timestamps are taken from the table when a round uses them. */
+    hko_bench_gen_trace(z, n_workers, T, write_pm, seed, tkey, top, tid);
     int32_t *rcount = calloc((size_t)n_workers * P, sizeof(int32_t));
-    {
-        const int64_t per_round = (int64_t)n_workers * rstride;
-        size_t hs = 1024;
-        while (hs < 2 * (size_t)(per_round ? per_round : 1)) hs <<= 1;
-        uint64_t *hk = malloc(hs * sizeof(uint64_t));
-        uint32_t *ids = malloc(sizeof(uint32_t) * (size_t)(per_round ? per_round : 1));
-        uint8_t *keep = malloc((size_t)(per_round ? per_round : 1));
-        for (int k = 0; k < P && rstride; k++) {
-            memset(hk, 0, hs * sizeof(uint64_t));
-            for (int64_t g = 0; g < per_round; g++) {
-                uint64_t r1 = sm64(seed ^ ((uint64_t)k << 40) ^ (0x9E37ull * (uint64_t)g));
-                ids[g] = (uint32_t)zipf_draw(z, (double)(r1 >> 11) * (1.0 / 9007199254740992.0));
-            }
-            /* peer-major over the worker-major draws: a (peer, id) pair's first occurrence wins */
-            for (int r = 0; r < n_peers; r++)
-                for (int w = 0; w < n_workers; w++)
-                    for (int j = 0; j < per_peer; j++) {
-                        int64_t g = (int64_t)w * rstride + (int64_t)r * per_peer + j;
-                        uint64_t key = (((uint64_t)r << 32) | ids[g]) + 1;
-                        size_t h = (size_t)(sm64(key) & (hs - 1));
-                        while (hk[h] != 0 && hk[h] != key) h = (h + 1) & (hs - 1);
-                        keep[g] = hk[h] == 0;
-                        hk[h] = key;
-                    }
-            for (int w = 0; w < n_workers; w++) {
-                int cnt = 0;
-                for (int r = 0; r < n_peers; r++)
-                    for (int j = 0; j < per_peer; j++) {
-                        int64_t g = (int64_t)w * rstride + (int64_t)r * per_peer + j;
-                        if (!keep[g]) continue;
-                        uint8_t peer = (uint8_t)(1 + r);
-                        size_t o = ((size_t)k * n_workers + w) * rstride + cnt++;
-                        uint8_t *x = rinv_pool + o * osz, *v = rval_pool + o * 16;
-                        uint64_t key = key_of(ids[g]);
-                        memcpy(x, &key, 8);
-                        x[8] = OPC_INV; x[9] = peer; x[10] = (uint8_t)sv; x[11] = peer;
-                        memset(x + 12, 0, 6);
-                        memset(x + 18, 'a' + peer, sv);
-                        memcpy(v, x, 16);
-                        v[8] = OPC_VAL;
-                    }
-                rcount[(size_t)k * n_workers + w] = cnt;
-            }
-        }
-        free(hk); free(ids); free(keep);
-    }
+    hko_bench_gen_peer_rounds(z, n_workers, n_peers, per_peer, P, osz, sv, seed, rinv_pool, rval_pool, rcount);
     pthread_barrier_t start;
     pthread_barrier_init(&start, NULL, (unsigned)n_threads + 1);
     bench_thread *th = calloc((size_t)n_threads, sizeof(bench_thread));

@@ -417,3 +417,56 @@ class Mirror:
             self._check_rw_state(rw_state, rws_in, st_before, rw_op.reshape(-1, self.g.sizes.op)[:, 9], what)
         self._table(what)
         self.launches += 1
+
+
+class GpuEngine:
+    """Runs the launches of a case of tests/inline_cases.py on the device through a deferred Mirror (which runs the
+    oracle twin and compares); the device's results go back into the case's arrays. layout: the layout every launch
+    must run in (True INLINE, False LOG) instead of the one the case names for it -- a table that does not prefer
+    INLINE, or one whose local launches have no inline kernels, runs the same case in LOG."""
+
+    def __init__(self, m: "Mirror", layout=None):
+        self.m, self.g, self.o, self.sizes, self.machine_id = m, m.g, m.o, m.g.sizes, m.g.machine_id
+        self.layout = layout
+
+    def check_table(self, what):
+        self.m.check_table(what)
+
+    def launch(self, btype, elems, n_batches, stride, mb, counts=None, offsets=None, rw=None, rw_stride=0, ns=None,
+               unique=False, rows=None, vals=False, inline=None):
+        import torch
+
+        def dev(a):
+            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
+        esz = elems.dtype.itemsize
+        t = dev(elems)
+        kw = {}
+        if counts is not None:
+            kw["counts"] = torch.from_numpy(np.ascontiguousarray(counts, np.int32)).cuda()
+        if offsets is not None:
+            kw["offsets"] = torch.from_numpy(np.ascontiguousarray(offsets, np.int32)).cuda()
+        if rw is not None:
+            kw["rw"], kw["rw_stride_bytes"] = dev(rw), rw_stride * rw.dtype.itemsize
+        if ns is not None:
+            kw["node_suspected"] = torch.from_numpy(ns.copy()).cuda()
+        if int(btype) in (int(L.BatchType.local_ops), int(L.BatchType.local_ops_after_membership_change)):
+            kw["state_out"] = torch.full((n_batches * stride,), 0xEE, dtype=torch.uint8, device="cuda")
+        if rows is not None:
+            kw["rows"] = rows
+            if rw is not None:   # the mirrors of the read_write_ops' state and opcode bytes, as the bench round keeps
+                kw["rw_state"] = torch.from_numpy(rw["state"].copy()).cuda()
+                kw["rw_opcodes"] = torch.from_numpy(rw["opcode"].copy()).cuda()
+            if vals:
+                kw["ack_out"] = torch.zeros(((rows[0] - 1) * rows[1] + stride) * 16, dtype=torch.uint8, device="cuda")
+        self.m.expect_inline = inline if self.layout is None else self.layout
+        self.m.batch(btype, t, n_batches, stride, esz, mb, unique=unique, **kw)
+        torch.cuda.synchronize()
+        got = t.cpu().numpy()
+        if rows is not None and rows[2] >= 0:   # the skip row is no part of the launch
+            lo, hi = rows[2] * rows[1] * esz, (rows[2] * rows[1] + stride) * esz
+            assert np.array_equal(got[lo:hi], elems.view(np.uint8).reshape(-1)[lo:hi]), "the skip row was written"
+        elems.view(np.uint8).reshape(-1)[:] = got
+        if rw is not None:
+            rw.view(np.uint8).reshape(-1)[:] = kw["rw"].cpu().numpy()
+        if ns is not None:
+            ns[:] = kw["node_suspected"].cpu().numpy()

@@ -12,7 +12,6 @@ tests/inline_cases.py), and the Mirror asserts it from the layout counters: no t
 The cases and their inputs are tests/inline_cases.py; tests/test_inline_cases_cpu.py shows on the oracle alone
 that they produce their outcomes on inline keys and on the others.
 """
-import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +21,9 @@ torch = pytest.importorskip("torch")
 from hermes_amd import layout as L  # noqa: E402
 from oracle.oracle import OracleKVS  # noqa: E402
 from tests import inline_cases as C  # noqa: E402
-from tests.helpers import Mirror  # noqa: E402
+from tests.helpers import GpuEngine, Mirror  # noqa: E402
 
 LOG, INLINE = 0, 1
-LOCAL_TYPES = (int(L.BatchType.local_ops), int(L.BatchType.local_ops_after_membership_change))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -42,54 +40,6 @@ def engine_path():
     kvs.HermesKV.default_flags = kvs.BATCH_ENGINE
     yield
     kvs.HermesKV.default_flags = 0
-
-
-class GpuEngine:
-    """Runs a case's launches on the device through a deferred Mirror (which runs the oracle twin and compares);
-    the device's results go back into the case's arrays."""
-
-    def __init__(self, m: Mirror):
-        self.m, self.g, self.o, self.sizes, self.machine_id = m, m.g, m.o, m.g.sizes, m.g.machine_id
-
-    def check_table(self, what):
-        self.m.check_table(what)
-
-    def launch(self, btype, elems, n_batches, stride, mb, counts=None, offsets=None, rw=None, rw_stride=0, ns=None,
-               unique=False, rows=None, vals=False, inline=None):
-        def dev(a):
-            return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda()
-        esz = elems.dtype.itemsize
-        t = dev(elems)
-        kw = {}
-        if counts is not None:
-            kw["counts"] = torch.from_numpy(np.ascontiguousarray(counts, np.int32)).cuda()
-        if offsets is not None:
-            kw["offsets"] = torch.from_numpy(np.ascontiguousarray(offsets, np.int32)).cuda()
-        if rw is not None:
-            kw["rw"], kw["rw_stride_bytes"] = dev(rw), rw_stride * rw.dtype.itemsize
-        if ns is not None:
-            kw["node_suspected"] = torch.from_numpy(ns.copy()).cuda()
-        if int(btype) in LOCAL_TYPES:
-            kw["state_out"] = torch.full((n_batches * stride,), 0xEE, dtype=torch.uint8, device="cuda")
-        if rows is not None:
-            kw["rows"] = rows
-            if rw is not None:   # the mirrors of the read_write_ops' state and opcode bytes, as the bench round keeps
-                kw["rw_state"] = torch.from_numpy(rw["state"].copy()).cuda()
-                kw["rw_opcodes"] = torch.from_numpy(rw["opcode"].copy()).cuda()
-            if vals:
-                kw["ack_out"] = torch.zeros(((rows[0] - 1) * rows[1] + stride) * 16, dtype=torch.uint8, device="cuda")
-        self.m.expect_inline = inline
-        self.m.batch(btype, t, n_batches, stride, esz, mb, unique=unique, **kw)
-        torch.cuda.synchronize()
-        got = t.cpu().numpy()
-        if rows is not None and rows[2] >= 0:   # the skip row is no part of the launch
-            lo, hi = rows[2] * rows[1] * esz, (rows[2] * rows[1] + stride) * esz
-            assert np.array_equal(got[lo:hi], elems.view(np.uint8).reshape(-1)[lo:hi]), "the skip row was written"
-        elems.view(np.uint8).reshape(-1)[:] = got
-        if rw is not None:
-            rw.view(np.uint8).reshape(-1)[:] = kw["rw"].cpu().numpy()
-        if ns is not None:
-            ns[:] = kw["node_suspected"].cpu().numpy()
 
 
 def make_pair(name, what, rmw=False, skew=0, machine_id=0):
