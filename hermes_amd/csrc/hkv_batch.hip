@@ -40,80 +40,9 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "hkv_exec.h"
-#include "hkv_internal.h"
+#include "hkv_batch_dev.h"   // BatchArgs, BatchPlan; k_small is in hkv_batch_small.hip
 
 namespace hkv {
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-// per-element stage between passes; kStCommit: the element's shadow holds its key's latest state
-// (committed to the entry by k_commit unless a later round's first candidate supersedes it)
-enum : uint8_t { kStDone = 0, kStCommit = 1, kStPend = 2 };
-enum { kCtrFbM = 1, kCtrFbL = 2 };  // fallback: mem cursor, list length
-
-struct BatchArgs {
-    uint8_t *elems;
-    const int32_t *counts;
-    const int32_t *offsets;      // packed INV/VAL launches (counts NULL, stride = n): batch offsets
-    const uint8_t *index;
-    uint8_t *log;
-    uint8_t *rw;
-    int32_t *ns_idx;
-    unsigned long long *fw;      // [log_cap / 64] F word per 64-B log line (table-wide), see fw_index
-    unsigned long long *fx, *fy; // [log_cap / 64] INV words X, Y (INV direct path; zero between launches)
-    unsigned long long *ft;      // [log_cap / 64][8] ACK words T (ACK direct path; epoch << 32 | ~i)
-    uint32_t fw_mask;
-    uint32_t *ent;               // [n] entry id of every element (kNone: skipped or missing)
-    uint8_t *st;                 // [n] stage (kSt*)
-    uint32_t *pf;                // [n] pending element: its key's first candidate of the last round
-    uint8_t *shadow;             // [cap][entry_size] entry image a round's first candidate produced
-    unsigned long long *mem;     // [2 cap] fallback (F_R, element) pairs of workgroups with more than kFbLds
-    uint32_t *fbl;               // [cap] fallback list: elements still pending after the last round
-    uint32_t *ctr;               // kCtr*
-    unsigned int *error_flags;
-    Geometry g;
-    int64_t n;
-    int64_t rw_stride;
-    int32_t stride;
-    int32_t esz;
-    int32_t type;
-    uint32_t rtag0;              // round 0's tag; round r uses rtag0 + r
-    uint8_t ltag;                // launch tag (1..255) in the seqlock byte of keys with a round-0 candidate
-    int32_t rounds;              // rounds after round 0 before the fallback
-    int32_t inv_direct;          // INV launch on the direct path (k_inv_resolve)
-    int32_t ack_direct;          // ACK launch on the direct path (k_ack_resolve)
-    uint8_t g_membership;
-    uint8_t w_ack_init;
-    int32_t *node_suspected;     // small launches write it themselves
-    int32_t n_batches;
-    const uint8_t *host_src;     // small launches staged in host memory (BatchLaunch)
-    uint8_t *host_dst;
-    uint8_t *dev_region;
-    uint64_t region_bytes;
-    uint32_t *done_flag;
-    uint32_t done_value;
-    unsigned long long *prof;    // HKV_SMALL_PROF: phase timestamps of k_small (debug)
-    const SmallBatch *hdr;       // mixed small launches: the batch headers (in dev_region)
-    uint8_t *state_out;          // local launches: each element's final state byte (may be NULL)
-    const uint8_t *opc;          // local launches: the caller's opcode mirror (may be NULL, see k_local_pre)
-    const uint8_t *patch;        // local direct path: pending header writes (hkv_batch_desc.d_patch), or NULL
-    uint16_t *fk;                // local launches with RMWs: [n] each round-0 candidate's kind of mutation (fk_kind,
-                                 // k_lookup), so k_resolve0_direct can resolve the elements after an absorbing F
-    uint64_t *hx;                // big local launches with patches (patch_in_resolve): [2 n] each patched element's
-                                 // header word (bytes 8..15) as patched and its op's last 8-byte word, from
-                                 // k_lookup for k_resolve0_direct; NULL otherwise
-    uint8_t *rws;                // ACK launches: read_write_ops state mirror (hkv_batch_desc.d_rw_state), or NULL
-    const uint8_t *rwo;          // ACK launches: read_write_ops opcode mirror (hkv_batch_desc.d_opcode_in), or NULL
-    int32_t n_rows, skip_row;    // HKV_BATCH_ROWS: rows applied in order (k_unique_rows), one skipped (-1: none)
-    int64_t row_stride;          // elements between rows
-    int32_t dbg;                 // HKV_DBG: timing experiments that skip work (results invalid); always 0
-                                 // unless the library is built with -DHKV_DEBUG_MODES (HKV_DBG_ON)
-    int32_t check_unique;        // HKV_CHECK_UNIQUE: HKV_BATCH_UNIQUE launches verify their keys are unique
-    uint8_t *ack_out;            // INV launches: each element's ACK (hkv_batch_desc.d_ack_out), or NULL
-    uint32_t ack_out_size;
-    uint8_t *line;               // the inline residency (128 B per bucket), read and written by the <.., IL = true>
-                                 // instances only; NULL for every other launch
-};
 
 // Rounds after round 0 per batch type: how often a hot key usually mutates in one launch beyond
 // the first time. An ACK batch sets an ack bit and then completes; INVs carry at most a few
@@ -214,19 +143,6 @@ __device__ __forceinline__ uint8_t inv_opcode(uint8_t in, bool oog)
     return oog ? kInvOutOfGroup : (in == kOpInvAbort || in == kInvOutOfGroup) ? in : kInvSuccess;
 }
 
-__device__ __forceinline__ Ctx make_ctx(const BatchArgs &a)
-{
-    Ctx c;
-    c.g = a.g;
-    c.g_membership = a.g_membership;
-    c.w_ack_init = a.w_ack_init;
-    c.rw = nullptr;
-    c.rws = nullptr;
-    c.rw_done = nullptr;
-    c.vc = nullptr;
-    return c;
-}
-
 // The batch holding element i and its first element: i / stride, or for a packed launch the last
 // batch whose offset is <= i (empty batches share their successor's offset)
 __device__ __forceinline__ int32_t batch_of(const BatchArgs &a, int64_t i, int64_t &start)
@@ -267,8 +183,6 @@ __device__ __forceinline__ void note_state(const BatchArgs &a, int64_t i, const 
     if (a.state_out) a.state_out[i] = x[9];
 }
 
-__device__ __forceinline__ uint64_t phys_of(const BatchArgs &a, uint32_t e) { return (uint64_t)e * a.g.entry_unit; }
-__device__ __forceinline__ uint8_t *entry_of(const BatchArgs &a, uint32_t e) { return a.log + phys_of(a, e); }
 // Inline instances (IL): an entry id of the local launch's scratch carries "this key's entry lives in its
 // bucket's line" in bit 31 (ids stay below it while log_cap <= kInlineMaxLog). A key's identity -- F/X/Y/T
 // words, phys_of, fw_index -- stays its log offset; only the bytes' home differs, and that is a function of the
@@ -439,11 +353,6 @@ __device__ __forceinline__ void apply_to_shadow_wave(const BatchArgs &a, bool ca
 // every VAL of a launch compares against its key's timestamp at launch start, sets VALID iff they
 // match and reports VAL_SUCCESS whatever the state. The VALs of a key commute, and the matching
 // ones all store the same state byte.
-// 16 bytes at an 8-byte aligned address (op headers, log lines): one dwordx4 access
-struct __attribute__((aligned(8))) U64x2 {
-    uint64_t a, b;
-};
-
 // esz (a multiple of 8) bytes between 8-byte aligned buffers, 16 B per access
 __device__ __forceinline__ void copy_elem(uint8_t *dst, const uint8_t *src, int32_t esz)
 {
@@ -1132,10 +1041,7 @@ __global__ __launch_bounds__(BP) void k_resolve0(BatchArgs a)
 // all their loads are issued before the first store, so a wave waits one memory latency per
 // kVcBatch values instead of one per value. Every lane of the wave
 // calls it.
-#ifndef HKV_VC_BATCH_N
-#define HKV_VC_BATCH_N 4
-#endif
-constexpr int kVcBatch = HKV_VC_BATCH_N;
+constexpr int kVcBatch = 4;
 template <int VB>
 __device__ __forceinline__ void wave_value_copies_n(const VCopy &v, uint32_t n)
 {
@@ -1256,15 +1162,10 @@ __device__ __forceinline__ void wave_value_words_n(const VCopy &v, uint32_t n)
     }
 }
 
-#ifndef HKV_FULL_HDR
-#define HKV_FULL_HDR 1
-#endif
-#ifndef HKV_VC_WORDS
-#define HKV_VC_WORDS 1
-#endif
+// by words where the value allows it; values over 496 B take the byte-wise copies
 __device__ __forceinline__ void wave_value_copies(const VCopy &v, uint32_t n, int batch)
 {
-    if (HKV_VC_WORDS && n <= 8 * 62) {   // nw + 1 <= 64 source words
+    if (n <= 8 * 62) {   // nw + 1 <= 64 source words
         if (batch == 1) wave_value_words_n<1>(v, n);
         else wave_value_words_n<kVcBatch>(v, n);
         return;
@@ -1374,12 +1275,8 @@ __device__ __forceinline__ void wave_whole_ops(uint8_t *xg, bool whole, uint64_t
 // waves per SIMD k_resolve0_direct is compiled for (its registers: 512 / waves). At 8 it fits 64 VGPRs
 // instead of 127 (4 waves per SIMD): configs[2] fresh 0.736-0.741 -> 0.772-0.782 G ops/s (gpurun_out/r06s;
 // in round 5's kernel, before the patches, it was level)
-#ifndef HKV_R0D_WAVES
-#define HKV_R0D_WAVES 8
-#endif
-#define HKV_R0D_ATTR __attribute__((amdgpu_waves_per_eu(HKV_R0D_WAVES, 8)))
 template <int TYPE, int SV>
-__global__ __launch_bounds__(256) HKV_R0D_ATTR void k_resolve0_direct(BatchArgs a)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_resolve0_direct(BatchArgs a)
 {
     constexpr bool kPir = TYPE == kLocal && SV != 31;
     __shared__ uint64_t sop[kPir ? 256 * 3 : 1];
@@ -1488,7 +1385,6 @@ __global__ __launch_bounds__(256) HKV_R0D_ATTR void k_resolve0_direct(BatchArgs 
         return;
     }
     note_state(a, i, xg);
-#if HKV_FULL_HDR
     // the op's first three and last 8-byte words stored again as they now stand, so that with the value a
     // GET copied the slab's lines are written whole (a line written with holes costs HBM a read-modify-write:
     // tools/write_bench.hip, 4M 312-byte ops with an 8-byte hole each 495 us against 241 us whole)
@@ -1501,7 +1397,6 @@ __global__ __launch_bounds__(256) HKV_R0D_ATTR void k_resolve0_direct(BatchArgs 
         o[2] = h2;
         o[a.esz / 8 - 1] = t;
     }
-#endif
 }
 
 // ------------------------------------------------------------------ local launches: direct path
@@ -1533,19 +1428,10 @@ __global__ __launch_bounds__(256) HKV_R0D_ATTR void k_resolve0_direct(BatchArgs 
 // halves shared, and the two head elements per thread instead of four cut registers. Same box, 3 x 20
 // steps (gpurun_out/r05v): prepass 76.1 -> 64.2 us, 4.25-4.29 -> 4.27-4.36 G ops/s; 1536 (86 us), 4096 (78 us),
 // a 2048-element head (79 us) and a 4096-slot table (111 us) were slower
-#ifndef HKV_PRE_ELEMS
-#define HKV_PRE_ELEMS 2048
-#endif
-constexpr int kPreElems = HKV_PRE_ELEMS;   // elements per k_local_pre block (HKV_PRE_ELEMS: a build macro for A/B)
+constexpr int kPreElems = 2048;            // elements per k_local_pre block
 constexpr int kPreThreads = kPreElems / 4; // four of its own elements per thread
-#ifndef HKV_PRE_HEAD_ELEMS
-#define HKV_PRE_HEAD_ELEMS 1024
-#endif
-constexpr int kPreHead = HKV_PRE_HEAD_ELEMS;   // launch head whose PUT keys every block knows
-#ifndef HKV_PRE_HASH_SLOTS
-#define HKV_PRE_HASH_SLOTS 2048
-#endif
-constexpr int kPreHash = HKV_PRE_HASH_SLOTS;   // LDS slots of a (key -> first PUT) table (a power of two)
+constexpr int kPreHead = 1024;             // launch head whose PUT keys every block knows
+constexpr int kPreHash = 2048;             // LDS slots of a (key -> first PUT) table (a power of two)
 constexpr int kLfElems = 32;             // elements per k_local_fused block (one wave)
 enum { kCtrDefer = 3 };
 enum : uint8_t { kStDefer = 3 };
@@ -1679,24 +1565,12 @@ __device__ __forceinline__ void pre_insert_key(uint64_t *hk, uint64_t key)
 // keys of the PUTs among the launch's first kPreHead elements (before its own; headers only,
 // L2-resident after the first block) and drops its keys that have a PUT there -- an earlier block
 // offers that one. Four keys per lane group are in flight; the offer is a plain atomicMin.
-#ifndef HKV_PRE_PAIR
-#define HKV_PRE_PAIR 4
-#endif
-constexpr int kPrePair = HKV_PRE_PAIR;   // keys per lane group in flight in the prepass's lookups (a build macro for A/B)
-#ifdef HKV_PRE_WAVES
-#define HKV_PRE_ATTR __attribute__((amdgpu_waves_per_eu(HKV_PRE_WAVES)))
-#else
-#define HKV_PRE_ATTR
-#endif
+constexpr int kPrePair = 4;   // keys per lane group in flight in the prepass's lookups (2 or 8 were slower: DESIGN 6,
+                              // round 5). No occupancy or SGPR attribute: neither moved the prepass
 // No seqlock-byte tags (round 5): k_local_fused loads every hit's F word beside its log line and needs
 // no mark of the keys that have one
-#ifdef HKV_PRE_NUM_SGPR
-#define HKV_PRE_SGPR_ATTR __attribute__((amdgpu_num_sgpr(HKV_PRE_NUM_SGPR)))
-#else
-#define HKV_PRE_SGPR_ATTR
-#endif
 template <int HEAD = kPreHead, bool IL = false>
-__global__ __launch_bounds__(kPreThreads) HKV_PRE_ATTR HKV_PRE_SGPR_ATTR void k_local_pre(BatchArgs a)
+__global__ __launch_bounds__(kPreThreads) void k_local_pre(BatchArgs a)
 {
     __shared__ uint64_t hk[kPreHash], gk[kPreHash];  // the block's PUT keys, the head's
     __shared__ uint32_t hv[kPreHash];
@@ -1886,27 +1760,16 @@ __device__ __forceinline__ void local_resolve_nm(const BatchArgs &a, uint8_t *x,
 // per lane, so the exec code's branches are paid once per 32 elements; the ops go back whole.
 // Every hit's F word is loaded beside its log line; the word alone says whether this launch's prepass
 // offered a first candidate for the key (first_cand)
-// SGPR budget of the local launch's kernels (HKV_LOCAL_NUM_SGPR, a build macro for A/B): waves are admitted
+// SGPR budget of k_local_fused, 80 (round 6: local launch 353-355 -> 341-351 us, 7 -> 8 waves per SIMD): waves are admitted
 // per SIMD by ~800 SGPRs / (ceil(sgpr/16) * 16 + 16) (MI355X_MICROARCH.md, "Residency"), so 92 SGPRs allow
 // 7 waves and 80 allow 8
-#ifndef HKV_LOCAL_NUM_SGPR
-#define HKV_LOCAL_NUM_SGPR 80   // round 6: local launch 353-355 -> 341-351 us (gpurun_out/r06c), 7 -> 8 waves per SIMD
-#endif
-#if HKV_LOCAL_NUM_SGPR > 0
-#define HKV_LOCAL_SGPR_ATTR __attribute__((amdgpu_num_sgpr(HKV_LOCAL_NUM_SGPR)))
-#else
-#define HKV_LOCAL_SGPR_ATTR
-#endif
 // NW waves per block (round 6): each wave works on its own 32 elements as before, and after the block's
 // barrier the stage bytes and the state mirror of all NW * 32 elements go out as whole 64-byte blocks (a
 // wave's 32 bytes alone are half a block, which HBM writes with a read-modify-write: tools/calib_bench.hip,
 // 16-B random writes 2.4x the time of 64-B ones).
-#ifndef HKV_LF_WAVES
-#define HKV_LF_WAVES 2
-#endif
-constexpr int kLfWaves = HKV_LF_WAVES;   // waves per k_local_fused block (a build macro for A/B)
+constexpr int kLfWaves = 2;   // waves per k_local_fused block
 template <int P, int NW, bool IL = false>
-__global__ __launch_bounds__(64 * NW) HKV_LOCAL_SGPR_ATTR void k_local_fused(BatchArgs a)
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_sgpr(80))) void k_local_fused(BatchArgs a)
 {
     constexpr int E = 16 * P;   // elements per wave: P per lane group
     constexpr int EB = E * NW;  // elements per block
@@ -2286,18 +2149,9 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 // of the entry -- exactly the rows' launches one after another, since each row holds the key once --
 // and each element and the entry line are written back where they changed. An ACK's completion finds
 // its read_write_ops once per position (the rows share the batch layout).
-#ifdef HKV_ROWS_NUM_SGPR
-#define HKV_ROWS_SGPR_ATTR __attribute__((amdgpu_num_sgpr(HKV_ROWS_NUM_SGPR)))
-#else
-#define HKV_ROWS_SGPR_ATTR
-#endif
+// No SGPR or occupancy attribute: 80 SGPRs and 8 waves per SIMD were within box noise.
 template <int TYPE, int RMAX, int CH, int P = kLookupPair, bool IL = false>
-#ifdef HKV_ROWS_WAVES   // (A/B builds) waves per SIMD k_unique_rows is compiled for
-#define HKV_ROWS_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(HKV_ROWS_WAVES, 8)))
-#else
-#define HKV_ROWS_WAVES_ATTR
-#endif
-__global__ __launch_bounds__(64) HKV_ROWS_SGPR_ATTR HKV_ROWS_WAVES_ATTR void k_unique_rows(BatchArgs a)
+__global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
 {
     constexpr int E = 16 * P;   // positions per wave: P per lane group
     // CH: 16-B chunks of an element held in LDS (1 for 16-B ACKs, 4 for 56-B INVs)
@@ -2905,343 +2759,6 @@ __global__ __launch_bounds__(kFbThreads) void k_fb_exec(BatchArgs a)
     }
 }
 
-// ------------------------------------------------------------------ small launches
-// Launches of at most kSmallMax elements (the drop-in entry point's combined host batches, a
-// few hundred to a few thousand elements) run in ONE workgroup and ONE kernel: the launch-wide
-// latency of the multi-kernel engine (lookup, resolve, commit passes) is what bounds them, not
-// bandwidth. The same rounds, with the workgroup's barriers instead of kernel boundaries:
-//   lookup     every element (four per thread) as hermesKV.c:938-993; entry ids in LDS
-//   round r    pending elements test would_mutate against their key's entry as it stands
-//              (S_r); candidates lower their key's F in an LDS hash table (entry id -> F);
-//              barrier; elements before F (or of keys without one) resolve on private copies of
-//              S_r; barrier; F applies to the entry itself (S_r -> S_{r+1}); barrier.
-//   after kSmallRounds rounds, keys still mutating are finished serially: the smallest pending
-//   element of each key walks its key's pending elements in element order.
-// Exactness is the engine's (would_mutate sound, checked through *error_flags).
-constexpr int kSmallMax = (int)kSmallMaxElems;
-constexpr int kSmallThreads = 1024;
-constexpr int kSmallPer = kSmallMax / kSmallThreads;
-constexpr int kSmallSlots = 2 * kSmallMax;
-constexpr int kSmallRounds = 8;
-
-__device__ __forceinline__ uint32_t small_slot(uint32_t *hkey, uint32_t e)
-{
-    uint32_t h = (e * 0x9E3779B1u) >> (32 - 13);  // kSmallSlots = 2^13
-    for (;;) {
-        const uint32_t old = atomicCAS(&hkey[h], kNone, e);
-        if (old == kNone || old == e) return h;
-        h = (h + 1) & (kSmallSlots - 1);
-    }
-}
-
-// Where element i of a small launch lives. Uniform launches: n_batches batches of one type at
-// `stride` elements each (hkv_batch_async). Mixed launches (the combining submit of the host entry
-// point): batches of any type back to back, each described by a SmallBatch header, element i in
-// the batch b with bstart[b] <= i < bstart[b + 1].
-struct SmallView {
-    uint8_t *x;
-    uint8_t idx;      // op buffer index (local batches: < 256)
-    int32_t pos;      // the element's position in its batch (INV batches run to 900 and beyond)
-    int type;
-    int b;
-    bool live;
-};
-
-template <bool MIXED>
-__device__ __forceinline__ SmallView small_at(const BatchArgs &a, const int32_t *bstart, const SmallBatch *bh,
-                                              int i, Ctx &c)
-{
-    SmallView v;
-    if (!MIXED) {
-        const int32_t b = i / a.stride, idx = i - b * a.stride;
-        v.x = a.elems + (int64_t)i * a.esz;
-        v.idx = (uint8_t)idx;
-        v.pos = idx;
-        v.type = a.type;
-        v.b = b;
-        v.live = a.counts == nullptr || idx < a.counts[b];
-        c.rw = a.rw ? a.rw + (int64_t)b * a.rw_stride : nullptr;
-        c.rws = a.rws ? a.rws + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
-        c.rwo = a.rwo ? a.rwo + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
-        return v;
-    }
-    int lo = 0, hi = a.n_batches;  // the last b with bstart[b] <= i
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (bstart[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    const SmallBatch &h = bh[lo];
-    const int idx = i - bstart[lo];
-    v.x = a.dev_region + h.elem_off + (int64_t)idx * h.esz;
-    v.idx = (uint8_t)idx;
-    v.pos = idx;
-    v.type = h.type;
-    v.b = lo;
-    v.live = true;
-    c.g_membership = h.g_membership;
-    c.w_ack_init = h.w_ack_init;
-    c.rw = h.rw_off >= 0 ? a.dev_region + h.rw_off : nullptr;
-    c.rws = nullptr;
-    return v;
-}
-
-template <int SV, bool MIXED>
-__global__ __launch_bounds__(kSmallThreads) void k_small(BatchArgs a)
-{
-    extern __shared__ uint32_t lds[];
-    uint32_t *eid = lds;                          // [kSmallMax] entry id, kNone: skipped / missing / done
-    uint32_t *hkey = eid + kSmallMax;             // [kSmallSlots] entry id of the slot
-    uint32_t *hf = hkey + kSmallSlots;            // [kSmallSlots] the key's first candidate this round
-    int32_t *ns = reinterpret_cast<int32_t *>(hf + kSmallSlots);      // [kSmallMax] per batch: last membership change
-    uint16_t *slot = reinterpret_cast<uint16_t *>(ns + kSmallMax);    // [kSmallMax]
-    __shared__ int32_t bstart[kSmallMaxBatches + 1];
-    __shared__ SmallBatch bh[MIXED ? kSmallMaxBatches : 1];
-    const int tid = threadIdx.x;
-    const int n = (int)a.n;
-    if (a.prof && tid == 0) a.prof[0] = wall_clock64();
-    if (a.region_bytes) {  // staged in host memory: bring the launch's region into HBM (the
-                           // dispatch's system-scope acquire drops any line an earlier launch left)
-        const uint4 *src = reinterpret_cast<const uint4 *>(a.host_src);
-        uint4 *dst = reinterpret_cast<uint4 *>(a.dev_region);
-        for (uint64_t w = tid; w < a.region_bytes / 16; w += kSmallThreads) dst[w] = src[w];
-        __threadfence_block();
-    }
-    for (int j = tid; j < kSmallSlots; j += kSmallThreads) {
-        hkey[j] = kNone;
-        hf[j] = kNone;
-    }
-    for (int j = tid; j < a.n_batches && j < kSmallMax; j += kSmallThreads) ns[j] = -1;
-    if (MIXED) {
-        __syncthreads();  // the copied-in headers
-        const SmallBatch *g = reinterpret_cast<const SmallBatch *>(a.dev_region);
-        for (int j = tid; j < a.n_batches; j += kSmallThreads) bh[j] = g[j];
-        if (tid == 0) {
-            int32_t acc = 0;
-            for (int j = 0; j < a.n_batches; ++j) {
-                bstart[j] = acc;
-                acc += g[j].count;
-            }
-            bstart[a.n_batches] = acc;
-        }
-    }
-    __syncthreads();
-    if (a.prof && tid == 0) a.prof[1] = wall_clock64();
-    Ctx c = make_ctx(a);
-    // lookup (hermesKV.c:938-993); a hit reads the key and its meta S_0 from the log line at once
-    Meta m0[kSmallPer];
-    uint32_t pend = 0;  // bit k: element tid + k * kSmallThreads is pending
-#pragma unroll
-    for (int k = 0; k < kSmallPer; ++k) {
-        const int i = tid + k * kSmallThreads;
-        if (i >= n) continue;
-        uint32_t e = kNone;
-        const SmallView v = small_at<MIXED>(a, bstart, bh, i, c);
-        if (v.live) {
-            const U64x2 h = *reinterpret_cast<const U64x2 *>(v.x);
-            if (skip_elem_os(v.type, (uint8_t)h.b, (uint8_t)(h.b >> 8))) {
-                if (v.type == kInvs) atomicMax(&ns[v.b], v.pos);   // hermes_skip_inv: the last one wins
-            } else {
-                const uint64_t key = h.a;
-                const uint4 *bk = reinterpret_cast<const uint4 *>(a.index + ((key & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u);
-                const uint4 q0 = bk[0], q1 = bk[1], q2 = bk[2], q3 = bk[3];
-                const uint64_t sl[8] = {(uint64_t)q0.x | ((uint64_t)q0.y << 32), (uint64_t)q0.z | ((uint64_t)q0.w << 32),
-                                        (uint64_t)q1.x | ((uint64_t)q1.y << 32), (uint64_t)q1.z | ((uint64_t)q1.w << 32),
-                                        (uint64_t)q2.x | ((uint64_t)q2.y << 32), (uint64_t)q2.z | ((uint64_t)q2.w << 32),
-                                        (uint64_t)q3.x | ((uint64_t)q3.y << 32), (uint64_t)q3.z | ((uint64_t)q3.w << 32)};
-                const uint32_t tag = (uint32_t)(key >> 48);
-                int hit = -1;
-#pragma unroll
-                for (int q = 7; q >= 0; --q)
-                    if ((sl[q] & 1u) && ((uint32_t)(sl[q] >> 1) & 0x7FFFFFu) == tag) hit = q;
-                if (hit >= 0) {
-                    const uint64_t off = sl[hit] >> 24;
-                    if (a.g.log_head - off < a.g.log_cap) {
-                        const uint64_t phys = off & a.g.log_mask;
-                        const U64x2 *ln = reinterpret_cast<const U64x2 *>(a.log + phys);
-                        const U64x2 l0 = ln[0], l1 = ln[1], l2 = ln[2];  // key at 8, meta at 16..32
-                        if (l0.b == key) {
-                            e = (uint32_t)(phys / a.g.entry_unit);
-                            m0[k].w4 = (uint32_t)l1.a;
-                            m0[k].w5 = (uint32_t)(l1.a >> 32);
-                            m0[k].ver = (uint32_t)l1.b;
-                            m0[k].llw_cid = (uint8_t)(l1.b >> 32);
-                            m0[k].llw_ver = (uint32_t)(l1.b >> 40) | ((uint32_t)(l2.a & 0xFFu) << 24);
-                        }
-                    }
-                }
-                if (e == kNone) v.x[9] = kMiss;
-            }
-        }
-        eid[i] = e;
-        if (e != kNone) {
-            slot[i] = (uint16_t)small_slot(hkey, e);
-            pend |= 1u << k;
-        }
-    }
-    __syncthreads();
-    if (a.prof && tid == 0) a.prof[2] = wall_clock64();
-    bool any = true;
-    for (int r = 0;; ++r) {
-        any = __syncthreads_or(pend != 0);
-        if (!any || r == kSmallRounds) break;
-        // round 0 tests S_0 from the lookup's registers, later rounds the entry as it now stands
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k) {  // candidates of round r
-            if (!(pend >> k & 1u)) continue;
-            const int i = tid + k * kSmallThreads;
-            const SmallView v = small_at<MIXED>(a, bstart, bh, i, c);
-            if (r > 0) meta_load(entry_of(a, eid[i]), m0[k]);
-            if (would_mutate(v.type, v.x, m0[k], c)) atomicMin(&hf[slot[i]], (uint32_t)i);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k) {  // before the key's candidate: S_r, unchanged
-            if (!(pend >> k & 1u)) continue;
-            const int i = tid + k * kSmallThreads;
-            if (hf[slot[i]] <= (uint32_t)i) continue;
-            const SmallView v = small_at<MIXED>(a, bstart, bh, i, c);
-            Meta t = m0[k];
-            dispatch<SV>(v.type, v.x, entry_of(a, eid[i]), v.idx, t, c);
-            if (a.error_flags && !meta_equal(t, m0[k])) atomicOr(a.error_flags, 1u);
-            pend &= ~(1u << k);
-        }
-        __threadfence_block();
-        __syncthreads();  // every read of S_r precedes the mutation
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k) {  // the candidate: S_r -> S_{r+1}
-            if (!(pend >> k & 1u)) continue;
-            const int i = tid + k * kSmallThreads;
-            if (hf[slot[i]] != (uint32_t)i) continue;
-            const SmallView v = small_at<MIXED>(a, bstart, bh, i, c);
-            uint8_t *entry = entry_of(a, eid[i]);
-            Meta m = m0[k];
-            dispatch<SV>(v.type, v.x, entry, v.idx, m, c);
-            meta_store(entry, m);
-            hf[slot[i]] = kNone;
-            pend &= ~(1u << k);
-        }
-        __threadfence_block();
-    }
-    if (a.prof && tid == 0) a.prof[3] = wall_clock64();
-    if (any) {  // keys that kept mutating: the first pending element of each key finishes it in order
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k) {
-            const int i = tid + k * kSmallThreads;
-            if (i < n && !(pend >> k & 1u)) eid[i] = kNone;   // done: no longer part of any key's walk
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k)
-            if (pend >> k & 1u) atomicMin(&hf[slot[tid + k * kSmallThreads]], (uint32_t)(tid + k * kSmallThreads));
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < kSmallPer; ++k) {
-            const int i = tid + k * kSmallThreads;
-            if (!(pend >> k & 1u) || hf[slot[i]] != (uint32_t)i) continue;
-            const uint32_t e = eid[i];
-            uint8_t *entry = entry_of(a, e);
-            Meta m;
-            meta_load(entry, m);
-            for (int j = i; j < n; ++j) {
-                if (eid[j] != e) continue;
-                const SmallView v = small_at<MIXED>(a, bstart, bh, j, c);
-                dispatch<SV>(v.type, v.x, entry, v.idx, m, c);
-            }
-            meta_store(entry, m);
-        }
-    }
-    // hermes_skip_dispatcher's *node_suspected = value[0] of each INV batch's last membership change
-    if (MIXED) {
-        __syncthreads();
-        for (int b = tid; b < a.n_batches; b += kSmallThreads) {
-            const SmallBatch &h = bh[b];
-            if (h.type == kInvs && h.ns_off >= 0 && ns[b] >= 0)
-                *reinterpret_cast<int32_t *>(a.dev_region + h.ns_off) =
-                    a.dev_region[h.elem_off + (int64_t)ns[b] * h.esz + kOpValueOff];
-        }
-    } else if (a.type == kInvs && a.node_suspected) {
-        __syncthreads();
-        for (int b = tid; b < a.n_batches; b += kSmallThreads)
-            if (ns[b] >= 0) a.node_suspected[b] = a.elems[((int64_t)b * a.stride + ns[b]) * a.esz + kOpValueOff];
-    }
-    if (!MIXED && a.state_out) {
-        __syncthreads();
-        for (int i = tid; i < n; i += kSmallThreads) a.state_out[i] = a.elems[(int64_t)i * a.esz + 9];
-    }
-    if (a.prof && tid == 0) a.prof[4] = wall_clock64();
-    if (a.region_bytes) {  // results back to the host staging, then the completion flag
-        __threadfence_block();  // one workgroup wrote the region: its CU's caches see it
-        __syncthreads();
-        // System-scope stores (sc0 sc1) write through L2 to the host, and a thread's vmcnt counts
-        // them done once they are visible there: each thread waits for its own, then the flag
-        // follows the barrier. A __threadfence_system() instead writes back all of L2, every entry
-        // this launch dirtied included (~10 us); plain stores would sit in L2 and reach the host
-        // later, over the set's next use.
-        const unsigned long long *src = reinterpret_cast<const unsigned long long *>(a.dev_region);
-        unsigned long long *dst = reinterpret_cast<unsigned long long *>(a.host_dst);
-        for (uint64_t w = tid; w < a.region_bytes / 8; w += kSmallThreads)
-            __hip_atomic_store(dst + w, src[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(a.done_flag, a.done_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    if (a.prof && tid == 0) a.prof[5] = wall_clock64();
-}
-
-int launch_small(const BatchArgs &a0, hipStream_t s)
-{
-    // HKV_SMALL_PROF=N: every N-th launch records its phase timestamps and prints the running
-    // average (debug; synchronises the stream)
-    static const int prof_every = getenv("HKV_SMALL_PROF") ? atoi(getenv("HKV_SMALL_PROF")) : 0;
-    static unsigned long long *prof = nullptr;
-    static long prof_n = 0;
-    static double prof_sum[5] = {0, 0, 0, 0, 0};
-    BatchArgs a = a0;
-    a.prof = nullptr;
-    const bool sample = prof_every > 0 && (++prof_n % prof_every) == 0;
-    if (sample) {
-        if (!prof && hipHostMalloc((void **)&prof, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return -3;
-        a.prof = prof;
-    }
-    const size_t lds = (size_t)4 * (2 * kSmallMax + 2 * kSmallSlots) + (size_t)2 * kSmallMax;
-    auto setup = [&](const void *f, int k) {
-        static bool done[6] = {false, false, false, false, false, false};
-        if (!done[k]) {
-            if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return false;
-            done[k] = true;
-        }
-        return true;
-    };
-#define HKV_SMALL(V, M)                                                                   \
-    do {                                                                                  \
-        if (!setup((const void *)k_small<V, M>, (V == 31 ? 0 : V == 287 ? 1 : 2) + (M ? 3 : 0))) return -3; \
-        hipLaunchKernelGGL((k_small<V, M>), dim3(1), dim3(kSmallThreads), lds, s, a);        \
-    } while (0)
-    const bool mixed = a.hdr != nullptr;
-    if (a.g.st_value == 31) {
-        if (mixed) HKV_SMALL(31, true);
-        else HKV_SMALL(31, false);
-    } else if (a.g.st_value == 287) {
-        if (mixed) HKV_SMALL(287, true);
-        else HKV_SMALL(287, false);
-    } else {
-        if (mixed) HKV_SMALL(0, true);
-        else HKV_SMALL(0, false);
-    }
-#undef HKV_SMALL
-    if (sample) {
-        hipStreamSynchronize(s);
-        static long k = 0;
-        ++k;
-        for (int p = 0; p < 5; ++p) prof_sum[p] += (double)(prof[p + 1] - prof[p]) * 10.0 / 1000.0;  // 100 MHz ticks -> us
-        fprintf(stderr, "[hkv] k_small phases (us, avg of %ld): copy-in+init %.2f lookup %.2f rounds %.2f fallback %.2f copy-out %.2f\n", k,
-                prof_sum[0] / k, prof_sum[1] / k, prof_sum[2] / k, prof_sum[3] / k, prof_sum[4] / k);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 // ------------------------------------------------------------------ partitioned host launches
 // The combining submit's launches on 64-B entries (HostPartLaunch, hkv_internal.h). Workgroup g
 // takes partition g of every batch: all elements of its keys, in element order, and no other
@@ -3792,53 +3309,6 @@ __global__ void k_node_suspected(const uint8_t *elems, const int32_t *ns_idx, in
     if (i >= 0) out[b] = elems[(base + i) * esz + kOpValueOff];
 }
 
-// ------------------------------------------------------------------ the inline residency's conversions
-// Four lanes per bucket, 16 B each (two slots). The inline key is the one in the bucket's lowest in-use slot:
-// chosen from the bucket alone, so the same key whenever the conversion runs (nothing is inserted under the
-// rounds). to_inline copies the bucket into the first half of its line with that slot flagged and the key's
-// whole 64-B entry into the second half; to_log copies the second half back to the entry's log offset. An
-// empty bucket's line holds the (empty) bucket and no flag; its second half is never read.
-template <bool TO_INLINE>
-__global__ __launch_bounds__(256) void k_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line,
-                                                        uint64_t num_bkts, uint64_t log_mask)
-{
-    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
-    const uint64_t b = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
-    const bool live = b < num_bkts;   // (the four lanes of a group share b: a group is live or idle as a whole)
-    uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (live) v = reinterpret_cast<const uint4 *>(index + b * 64u)[q];
-    const uint64_t s0 = (uint64_t)v.x | ((uint64_t)v.y << 32), s1 = (uint64_t)v.z | ((uint64_t)v.w << 32);
-    const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
-    const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
-    uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
-#pragma unroll
-    for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
-    const int first = o ? __ffs(o) - 1 : 0;
-    const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
-    if (!live) return;
-    uint4 *ln = reinterpret_cast<uint4 *>(line + b * 128u);
-    uint4 *ent = reinterpret_cast<uint4 *>(log + (off & log_mask));
-    if (TO_INLINE) {
-        if (o && (first >> 1) == q) {
-            if (first & 1) v.w |= (uint32_t)(kInlineSlotBit >> 32);
-            else v.y |= (uint32_t)(kInlineSlotBit >> 32);
-        }
-        ln[q] = v;
-        ln[4 + q] = o ? ent[q] : make_uint4(0u, 0u, 0u, 0u);
-    } else if (o) {
-        ent[q] = ln[4 + q];
-    }
-}
-
-int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uint64_t num_bkts, uint64_t log_mask,
-                          bool to_inline, hipStream_t s)
-{
-    const unsigned grid = (unsigned)((num_bkts + 63) / 64);
-    if (to_inline) hipLaunchKernelGGL(k_layout_convert<true>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
-    else hipLaunchKernelGGL(k_layout_convert<false>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 // ------------------------------------------------------------------ host side
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -3873,84 +3343,125 @@ size_t batch_fw_words(uint64_t log_cap) { return (size_t)(log_cap >> 6); }
 
 uint32_t batch_max_epoch() { return (1u << 29) - 1; }
 
-// The paths of launch_batch, decided in one place: launch_batch takes them, and batch_inline_capable tells the
-// runtime which of them have inline instances (the kernels a configs[1] round runs).
-struct BatchPath {
-    bool small, local_direct, rows, unique_lds64, vals;
-};
-static BatchPath batch_path(const BatchLaunch &bl)
+// ---- the plan: which engine runs a launch
+// Every predicate on a launch's geometry and flags is written here, once: launch_batch follows the plan, and
+// batch_inline_capable tells the runtime which launches have inline instances (the kernels a configs[1] round
+// runs). The engines are tested for in the order of Engine's members.
+static BatchPlan plan_batch(const BatchLaunch &bl)
 {
-    BatchPath p{};
+    BatchPlan p{};
     const int64_t n = bl.n;
-    p.small = (bl.path == kPathSmall || (bl.path == kPathAuto && n <= kSmallMaxElems)) && n <= kSmallMaxElems;
-    // local batches without RMWs in the default layout: the direct path (k_local_pre, k_local_fused)
-    p.local_direct = bl.type == kLocal && !bl.g.rmw_enabled && bl.esz == 56 && bl.g.st_value == 31 &&
-                     bl.g.entry_size == 64 && !bl.offsets;
-    const bool uniq = bl.unique && (bl.type == kInvs || bl.type == kAcks);
-    p.rows = bl.n_rows > 0 && bl.unique;
-    p.unique_lds64 = uniq && bl.g.st_value == 31 && bl.g.entry_size == 64 && bl.esz <= 64;
-    p.vals = bl.type == kVals;
+    if (n <= 0) return p;   // nothing runs (and nothing has an inline instance)
+    const int32_t type = bl.type;
+    const uint32_t sv = bl.g.st_value;
+    const bool rmw = bl.g.rmw_enabled != 0;
+    const bool geo64 = sv == 31 && bl.g.entry_size == 64;   // the default layout: 31-B values in 64-B entries
+    const bool local_type = type == kLocal || type == kLocalAfterMemb;
+    p.sv = sv == 31 ? 31 : sv == 287 ? 287 : 0;
+    p.big = bl.esz > 64;
+    p.mixed = bl.hdr != nullptr;
+    p.il = bl.line != nullptr;
+    p.inv_direct = type == kInvs && !rmw && n < kInvDirectMax;
+    p.ack_direct = type == kAcks && !rmw && n < (int64_t)kNone;
+    p.ack_out = bl.ack_out && (type == kInvs || (type == kAcks && bl.n_rows > 0));
+    p.state_out = local_type;
+    p.opc = type == kLocal;
+    p.fk = type == kLocal && rmw && p.big;
+    p.rw_mirrors = type == kAcks;
+
+    if ((bl.path == kPathSmall || (bl.path == kPathAuto && n <= kSmallMaxElems)) && n <= kSmallMaxElems) {
+        p.engine = Engine::kSmall;
+    } else if (type == kLocal && !rmw && bl.esz == 56 && geo64 && !bl.offsets) {
+        // local batches without RMWs in the default layout
+        p.engine = Engine::kLocalDirect;
+        p.inline_instance = true;
+    } else if (bl.n_rows > 0 && bl.unique) {   // HKV_BATCH_ROWS: one pass over positions of all rows
+        p.engine = Engine::kRows;
+        p.rmax = bl.n_rows <= 2 ? 2 : 8;
+        // elements of 16 B (ACKs without RMWs) keep one chunk each in LDS, others four
+        p.ch = type == kInvs ? 4 : bl.esz <= 16 ? 1 : 4;
+        // (k_unique_rows: 64-B entries and elements, checked by the runtime)
+        p.inline_instance = geo64 && !local_type && bl.n_rows <= 8;
+    } else if (bl.unique && (type == kInvs || type == kAcks)) {   // one pass: every key has one element
+        if (geo64 && bl.esz <= 64) {
+            p.engine = Engine::kUniqueLds64;
+            p.inline_instance = true;
+        } else if (type == kInvs && sv == 287 && bl.g.entry_size == 320 && bl.esz <= 320) {
+            // big-object INVs, whose raises copy 287-B values: staged through LDS (cfg3: 460 -> 326 us per
+            // round). ACKs touch the header and the meta only, so they stay in place (LDS-staged: 110 -> 191 us)
+            p.engine = Engine::kUniqueLdsBig;
+        } else {   // big-entry ACKs, other geometries
+            p.engine = Engine::kUniqueInPlace;
+            if (p.ack_out) p.refuse = -1;   // only the LDS-staged passes write the ACKs
+        }
+    } else if (type == kVals) {   // one pass (see k_lookup)
+        p.engine = Engine::kValsOnePass;
+        p.inline_instance = geo64;
+    } else {
+        // The head split pays off where one launch piles many candidates onto a few keys: local
+        // batches under Zipf. A replica's INVs and ACKs carry at most one write per key and peer per
+        // round, so those launches take one pass (their launch-sized head took ~9 us at cfg2).
+        p.lookup_head = local_type && n > kLookupHead ? kLookupHead : n;
+        p.slab_threads = p.big ? 128 : 256;
+        // big ops: local and ACK launches resolve round 0 in place (measured at cfg3: local 1.26 ->
+        // 1.05 ms, ACK 0.69 -> 0.55 ms); INV launches keep the LDS slab (0.40 vs 0.52 ms in place)
+        p.engine = p.ack_direct ? Engine::kRoundsAckDirect
+                   : p.inv_direct ? Engine::kRoundsInvDirect
+                   : p.big && type != kInvs ? Engine::kRoundsInPlace
+                                            : Engine::kRoundsSlab;
+    }
+    if (p.il && !p.inline_instance) p.refuse = -1;
+    if (bl.region_bytes && p.engine != Engine::kSmall) p.refuse = -1;   // host-staged launches are small ones
+    p.node_suspected = p.engine != Engine::kSmall && type == kInvs && bl.ns_idx && bl.node_suspected;
+
+    // big local launches on the rounds engine (configs[2]): k_lookup reads the patches, k_resolve0_direct writes
+    // the patched ops (patch_in_resolve, see there): values of at most 320 bytes, the op's pad after its value
+    // within its last 8-byte word
+    const uint32_t vend = (uint32_t)kOpValueOff + sv;
+    if (!bl.patch) p.patches = Patches::kNone;
+    else if (p.engine == Engine::kSmall) p.patches = Patches::kApplyFirst;
+    else if (p.engine == Engine::kLocalDirect) p.patches = Patches::kByEngine;
+    else if (type == kLocal && p.big && !bl.offsets && sv != 31 && sv <= 320 && bl.esz % 8 == 0 &&
+             (uint32_t)bl.esz >= vend && (uint32_t)bl.esz <= vend + 8)
+        p.patches = Patches::kInResolve;
+    else p.patches = Patches::kApplyFirst;
     return p;
 }
 
-bool batch_inline_capable(const BatchLaunch &bl)
-{
-    if (bl.n <= 0 || bl.g.entry_size != 64 || bl.g.st_value != 31) return false;
-    const BatchPath p = batch_path(bl);
-    if (p.small) return false;
-    if (p.local_direct) return true;
-    if (bl.type == kLocal || bl.type == kLocalAfterMemb) return false;
-    if (p.rows) return bl.n_rows <= 8;   // (k_unique_rows: 64-B entries and elements, checked by the runtime)
-    if (bl.unique && (bl.type == kInvs || bl.type == kAcks)) return p.unique_lds64;
-    return p.vals;
-}
+bool batch_inline_capable(const BatchLaunch &bl) { return plan_batch(bl).inline_instance; }
 
-int launch_batch(BatchLaunch &bl, hipStream_t s)
+// The kernels' argument block of one launch; a member nobody sets is zero
+static BatchArgs make_args(const BatchLaunch &bl, const BatchPlan &p)
 {
-    const int64_t n = bl.n;
-    if (n <= 0) return 0;
-    if (bl.line && !batch_inline_capable(bl)) return -1;
-    BatchArgs a;
-    a.elems = bl.elems;
-    a.counts = bl.counts;
-    a.offsets = bl.offsets;
-    a.state_out = (bl.type == kLocal || bl.type == kLocalAfterMemb) ? bl.state_out : nullptr;
-    a.opc = bl.type == kLocal ? bl.opcode_in : nullptr;
-    a.patch = nullptr;
-    a.hx = nullptr;
-    a.fk = bl.type == kLocal && bl.g.rmw_enabled && bl.esz > 64 ? bl.fk : nullptr;   // (k_resolve0_direct's launches)
-    a.ack_out = bl.type == kInvs || (bl.type == kAcks && bl.n_rows > 0) ? bl.ack_out : nullptr;
-    a.ack_out_size = bl.ack_out_size;
-    a.n_rows = bl.n_rows;
-    a.skip_row = bl.skip_row;
-    a.row_stride = bl.row_stride;
-    a.rws = bl.type == kAcks ? bl.rw_state : nullptr;
-    a.rwo = bl.type == kAcks ? bl.opcode_in : nullptr;
 #ifdef HKV_DEBUG_MODES
     static const int dbg_env = getenv("HKV_DBG") ? atoi(getenv("HKV_DBG")) : 0;
 #else
     constexpr int dbg_env = 0;   // the default build cannot skip work (tools/dbg_modes.sh builds its own)
 #endif
-    a.dbg = dbg_env;
     static const int check_unique_env = getenv("HKV_CHECK_UNIQUE") ? atoi(getenv("HKV_CHECK_UNIQUE")) : 0;
-    a.check_unique = check_unique_env;
+    BatchArgs a{};
+    a.elems = bl.elems;
+    a.counts = bl.counts;
+    a.offsets = bl.offsets;
     a.index = bl.index;
     a.log = bl.log;
-    a.line = bl.line;
     a.rw = bl.rw;
     a.ns_idx = bl.ns_idx;
     a.fw = bl.fw;
+    a.fx = bl.fx;
+    a.fy = bl.fy;
+    a.ft = bl.ft;
     a.fw_mask = (uint32_t)((bl.g.log_cap >> 6) - 1);
     a.ent = bl.ent;
     a.st = bl.st;
-    a.mem = bl.mem;
-    a.fbl = bl.fbl;
     a.pf = bl.pf;
     a.shadow = bl.shadow;
+    a.mem = bl.mem;
+    a.fbl = bl.fbl;
     a.ctr = bl.ctr;
     a.error_flags = bl.error_flags;
     a.g = bl.g;
-    a.n = n;
+    a.n = bl.n;
     a.rw_stride = bl.rw_stride;
     a.stride = bl.stride;
     a.esz = bl.esz;
@@ -3958,11 +3469,8 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
     a.rtag0 = bl.epoch << 3;
     a.ltag = (uint8_t)(bl.epoch % 255u + 1u);
     a.rounds = rounds_for(bl.type, bl.g.rmw_enabled != 0);
-    a.fx = bl.fx;
-    a.fy = bl.fy;
-    a.inv_direct = bl.type == kInvs && !bl.g.rmw_enabled && n < kInvDirectMax;
-    a.ft = bl.ft;
-    a.ack_direct = bl.type == kAcks && !bl.g.rmw_enabled && n < (int64_t)kNone;
+    a.inv_direct = p.inv_direct;
+    a.ack_direct = p.ack_direct;
     a.g_membership = bl.g_membership;
     a.w_ack_init = bl.w_ack_init;
     a.node_suspected = bl.node_suspected;
@@ -3974,156 +3482,184 @@ int launch_batch(BatchLaunch &bl, hipStream_t s)
     a.done_flag = bl.done_flag;
     a.done_value = bl.done_value;
     a.hdr = bl.hdr;
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    const unsigned cgrid = (unsigned)((n + 256 * kCandPer - 1) / (256 * kCandPer));
-    const bool big = bl.esz > 64;
-    // big ops: local and ACK launches resolve round 0 in place (measured at cfg3: local 1.26 ->
-    // 1.05 ms, ACK 0.69 -> 0.55 ms); INV launches keep the LDS slab (0.40 vs 0.52 ms in place)
-    const bool big_direct = bl.type != kInvs;
-    const unsigned rgrid = (unsigned)(big ? (n + 127) / 128 : grid);
-    const size_t rlds = (size_t)(big ? 128 : 256) * (size_t)bl.esz;
-    const BatchPath bp = batch_path(bl);
-    const bool small = bp.small;
-    if (bl.region_bytes && !small) return -1;  // host-staged launches are small ones
-    const bool local_direct = bp.local_direct;
-    const bool il = bl.line != nullptr;   // the inline instances (separate ones: a runtime branch in k_local_fused
-                                          // cost a wave of occupancy)
-    // big local launches on the rounds engine (configs[2]): k_lookup reads the patches, k_resolve0_direct writes
-    // the patched ops (patch_in_resolve, see there): values of at most 320 bytes, the op's pad after its value
-    // within its last 8-byte word
-    const uint32_t vend = (uint32_t)kOpValueOff + bl.g.st_value;
-    const bool patch_in_resolve = bl.patch && !small && !local_direct && bl.type == kLocal && big && big_direct &&
-                                  !bl.offsets && bl.g.st_value != 31 && bl.g.st_value <= 320 && bl.esz % 8 == 0 &&
-                                  (uint32_t)bl.esz >= vend && (uint32_t)bl.esz <= vend + 8;
-    if (patch_in_resolve) {
-        a.patch = bl.patch;
-        a.hx = bl.hx;
-    } else if (bl.patch && (small || !local_direct)) {  // the other paths take the patches as op writes first
-        hipLaunchKernelGGL(k_apply_patch, dim3(grid), dim3(256), 0, s, bl.elems, bl.patch, n, bl.esz, bl.g.st_value);
-    } else if (bl.patch) {
-        a.patch = bl.patch;
-    }
-    if (small) {
-        if (launch_small(a, s)) return -3;
-        return 0;                              // node_suspected written by the kernel
-    } else if (local_direct) {
-        const dim3 pgrid((unsigned)((n + kPreElems - 1) / kPreElems));
-        const dim3 fgrid((unsigned)((n + 32 * kLfWaves - 1) / (32 * kLfWaves)));
-        if (il) {
-            hipLaunchKernelGGL((k_local_pre<kPreHead, true>), pgrid, dim3(kPreThreads), 0, s, a);
-            hipLaunchKernelGGL((k_local_fused<2, kLfWaves, true>), fgrid, dim3(64 * kLfWaves), 0, s, a);
-            hipLaunchKernelGGL(k_local_deferred<true>, dim3(128u), dim3(256), 0, s, a);
-            hipLaunchKernelGGL(k_commit_w<true>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
-            return hipGetLastError() == hipSuccess ? 0 : -3;
-        }
-        hipLaunchKernelGGL(k_local_pre<kPreHead>, pgrid, dim3(kPreThreads), 0, s, a);
-        hipLaunchKernelGGL((k_local_fused<2, kLfWaves>), fgrid, dim3(64 * kLfWaves), 0, s, a);
-        // the waiting elements' count is on the device: enough workgroups for the rounds after a
-        // membership change (configs[4]: ~100 K elements of keys a failed peer left INVALID), which
-        // return at once when there are few
-        hipLaunchKernelGGL(k_local_deferred<false>, dim3(128u), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_commit_w<false>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
-    } else if (bl.n_rows > 0 && bl.unique) {  // HKV_BATCH_ROWS: one pass over positions of all rows
-        // two positions per lane group, 32 per wave
-        const unsigned lgrid = (unsigned)((n + kLfElems - 1) / kLfElems);
-        // elements of 16 B (ACKs without RMWs) keep one chunk each in LDS, others four
-#define HKV_ROWS(T, CH)                                                                                           \
-    do {                                                                                                         \
-        if (il && bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, kLookupPair, true>), dim3(lgrid), dim3(64), 0, s, a); \
-        else if (il) hipLaunchKernelGGL((k_unique_rows<T, 8, CH, kLookupPair, true>), dim3(lgrid), dim3(64), 0, s, a); \
-        else if (bl.n_rows <= 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH>), dim3(lgrid), dim3(64), 0, s, a);  \
-        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH>), dim3(lgrid), dim3(64), 0, s, a);                      \
-    } while (0)
-        if (bl.type == kInvs) HKV_ROWS(kInvs, 4);
-        else if (bl.esz <= 16) HKV_ROWS(kAcks, 1);
-        else HKV_ROWS(kAcks, 4);
-#undef HKV_ROWS
-    } else if (bl.unique && (bl.type == kInvs || bl.type == kAcks)) {  // one pass: every key has one element
-        // in-place unique pass (big-entry ACKs, other geometries): one element per lane group
-        const unsigned ugrid1 = (unsigned)((n + 63) / 64);
-#define HKV_UNIQUE(T)                                                                                  \
-    do {                                                                                               \
-        if (bl.g.st_value == 31) hipLaunchKernelGGL((k_unique<T, 31, 1>), dim3(ugrid1), dim3(256), 0, s, a); \
-        else if (bl.g.st_value == 287) hipLaunchKernelGGL((k_unique<T, 287, 1>), dim3(ugrid1), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((k_unique<T, 0, 1>), dim3(ugrid1), dim3(256), 0, s, a);             \
-    } while (0)
-        const bool lds64 = bl.g.st_value == 31 && bl.g.entry_size == 64 && bl.esz <= 64;
-        const bool lds_big = bl.type == kInvs && bl.g.st_value == 287 && bl.g.entry_size == 320 && bl.esz <= 320;
-        if (a.ack_out && !(lds64 || lds_big)) return -1;   // only the LDS-staged passes write the ACKs
-        if (lds64) {
-            // 64-B entries: the LDS-staged pass, one element per lane group (16 per wave). Same box, INV phase
-            // per step (gpurun_out/r04m, r04t): 72-77 us at 1 element per lane group, 78-80 at 2, 91 at 4
-            const unsigned g1 = (unsigned)((n + 15) / 16);
-            if (il && bl.type == kInvs) hipLaunchKernelGGL((k_unique_lds<kInvs, 1, true>), dim3(g1), dim3(64), 0, s, a);
-            else if (il) hipLaunchKernelGGL((k_unique_lds<kAcks, 1, true>), dim3(g1), dim3(64), 0, s, a);
-            else if (bl.type == kInvs) hipLaunchKernelGGL((k_unique_lds<kInvs, 1>), dim3(g1), dim3(64), 0, s, a);
-            else hipLaunchKernelGGL((k_unique_lds<kAcks, 1>), dim3(g1), dim3(64), 0, s, a);
-        } else if (lds_big) {
-            // big-object INVs, whose raises copy 287-B values: staged through LDS (cfg3: 460 -> 326 us per
-            // round). ACKs touch the header and the meta only, so they stay in place (LDS-staged: 110 -> 191 us)
-            hipLaunchKernelGGL(k_unique_big<kInvs>, dim3((unsigned)((n + kUbElems - 1) / kUbElems)), dim3(64), 0, s, a);
-        } else if (bl.type == kInvs) HKV_UNIQUE(kInvs);
-        else HKV_UNIQUE(kAcks);
-#undef HKV_UNIQUE
-    } else if (bl.type == kVals) {             // one pass (see k_lookup)
-        // one element per lane group. Same box, VAL batch per step (gpurun_out/r04m, r04u): 49.6-50.2 us at 1,
-        // 52.3-53.9 at 2, 57 at 4
-        if (il) hipLaunchKernelGGL((k_lookup<1, true>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, n);
-        else hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, n);
-        return hipGetLastError() == hipSuccess ? 0 : -3;
+    a.state_out = p.state_out ? bl.state_out : nullptr;
+    a.opc = p.opc ? bl.opcode_in : nullptr;
+    a.patch = p.patches == Patches::kInResolve || p.patches == Patches::kByEngine ? bl.patch : nullptr;
+    a.fk = p.fk ? bl.fk : nullptr;
+    a.hx = p.patches == Patches::kInResolve ? bl.hx : nullptr;
+    a.rws = p.rw_mirrors ? bl.rw_state : nullptr;
+    a.rwo = p.rw_mirrors ? bl.opcode_in : nullptr;
+    a.n_rows = bl.n_rows;
+    a.skip_row = bl.skip_row;
+    a.row_stride = bl.row_stride;
+    a.dbg = dbg_env;
+    a.check_unique = check_unique_env;
+    a.ack_out = p.ack_out ? bl.ack_out : nullptr;
+    a.ack_out_size = bl.ack_out_size;
+    a.line = bl.line;
+    return a;
+}
+
+// ---- the engines' launchers; each returns 0 or launch_batch's -3
+// Separate inline instances of the local kernels: a runtime branch in k_local_fused cost a wave of occupancy
+// 
+template <bool IL>
+static void launch_local_il(const BatchArgs &a, hipStream_t s)
+{
+    const int64_t n = a.n;
+    const dim3 pgrid((unsigned)((n + kPreElems - 1) / kPreElems));
+    const dim3 fgrid((unsigned)((n + 32 * kLfWaves - 1) / (32 * kLfWaves)));
+    hipLaunchKernelGGL((k_local_pre<kPreHead, IL>), pgrid, dim3(kPreThreads), 0, s, a);
+    hipLaunchKernelGGL((k_local_fused<2, kLfWaves, IL>), fgrid, dim3(64 * kLfWaves), 0, s, a);
+    // the waiting elements' count is on the device: enough workgroups for the rounds after a
+    // membership change (configs[4]: ~100 K elements of keys a failed peer left INVALID), which
+    // return at once when there are few
+    hipLaunchKernelGGL(k_local_deferred<IL>, dim3(128u), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_commit_w<IL>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
+}
+
+static int launch_local(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    if (p.il) launch_local_il<true>(a, s);
+    else launch_local_il<false>(a, s);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// k_unique_rows: two positions per lane group, 32 per wave
+template <int T, int CH>
+static void launch_rows(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    const unsigned lgrid = (unsigned)((a.n + kLfElems - 1) / kLfElems);
+    with_bool(p.il, [&](auto il) {
+        constexpr bool IL = decltype(il)::value;
+        if (p.rmax == 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
+    });
+}
+
+// the in-place pass and the 64-B LDS-staged one: one element per lane group (16 per wave). Same box, INV phase
+// per step (runs r04m, r04t): 72-77 us at 1 element per lane group, 78-80 at 2, 91 at 4
+template <int T>
+static void launch_unique_t(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    if (p.engine == Engine::kUniqueLds64) {
+        const unsigned g1 = (unsigned)((a.n + 15) / 16);
+        with_bool(p.il, [&](auto il) {
+            hipLaunchKernelGGL((k_unique_lds<T, 1, decltype(il)::value>), dim3(g1), dim3(64), 0, s, a);
+        });
     } else {
-    // The head split pays off where one launch piles many candidates onto a few keys: local
-    // batches under Zipf. A replica's INVs and ACKs carry at most one write per key and peer per
-    // round, so those launches take one pass (their launch-sized head took ~9 us at cfg2).
-    const bool split = bl.type == kLocal || bl.type == kLocalAfterMemb;
-    const int64_t head = split && n > kLookupHead ? kLookupHead : n;
-    // one element per lane group in the other lookups (configs[2] 0.627-0.635 against 0.620-0.622 G ops/s at
-    // two, same box, gpurun_out/r04v)
+        const unsigned ugrid1 = (unsigned)((a.n + 63) / 64);
+        with_sv(p.sv, [&](auto v) {
+            hipLaunchKernelGGL((k_unique<T, decltype(v)::value, 1>), dim3(ugrid1), dim3(256), 0, s, a);
+        });
+    }
+}
+
+static int launch_unique(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    if (p.engine == Engine::kRows) {
+        if (a.type == kInvs) launch_rows<kInvs, 4>(a, p, s);
+        else if (p.ch == 1) launch_rows<kAcks, 1>(a, p, s);
+        else launch_rows<kAcks, 4>(a, p, s);
+    } else if (p.engine == Engine::kUniqueLdsBig) {
+        hipLaunchKernelGGL(k_unique_big<kInvs>, dim3((unsigned)((a.n + kUbElems - 1) / kUbElems)), dim3(64), 0, s, a);
+    } else if (a.type == kInvs) {
+        launch_unique_t<kInvs>(a, p, s);
+    } else {
+        launch_unique_t<kAcks>(a, p, s);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// Round 0's resolve, the rounds, the commit and the fallback of one (batch type, value class)
+template <int T, int V>
+static int launch_rounds_tv(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((a.n + 255) / 256);
+    const unsigned cgrid = (unsigned)((a.n + 256 * kCandPer - 1) / (256 * kCandPer));
+    const unsigned rgrid = (unsigned)((a.n + p.slab_threads - 1) / p.slab_threads);
+    const size_t rlds = (size_t)p.slab_threads * (size_t)a.esz;
+    if (p.big && rlds > 64 * 1024 &&
+        hipFuncSetAttribute((const void *)k_resolve0<T, V, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds) !=
+            hipSuccess)
+        return -3;
+    if (p.engine == Engine::kRoundsInPlace) hipLaunchKernelGGL((k_resolve0_direct<T, V>), dim3(grid), dim3(256), 0, s, a);
+    else if (p.big) hipLaunchKernelGGL((k_resolve0<T, V, 128>), dim3(rgrid), dim3(128), rlds, s, a);
+    else hipLaunchKernelGGL((k_resolve0<T, V, 256>), dim3(rgrid), dim3(256), rlds, s, a);
+    for (int r = 1; r <= a.rounds; ++r) {
+        hipLaunchKernelGGL((k_cand<T>), dim3(cgrid), dim3(256), 0, s, a, r);
+        hipLaunchKernelGGL((k_resolve<T, V>), dim3(grid), dim3(256), V == 31 ? 256 * a.esz : 0, s, a, r);
+    }
+    hipLaunchKernelGGL((k_commit<V>), dim3(grid), dim3(256), 0, s, a);
+    if (a.rounds > 0) hipLaunchKernelGGL((k_fb_exec<T, V>), dim3(256), dim3(kFbThreads), 0, s, a);
+    return 0;
+}
+
+template <int T>
+static int launch_rounds_t(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    int rc = 0;
+    with_sv(p.sv, [&](auto v) { rc = launch_rounds_tv<T, decltype(v)::value>(a, p, s); });
+    return rc;
+}
+
+// kValsOnePass and the four rounds engines: all begin with k_lookup, one element per lane group. Same box, VAL
+// batch per step (runs r04m, r04u): 49.6-50.2 us at 1, 52.3-53.9 at 2, 57 at 4; configs[2] 0.627-0.635 against
+// 0.620-0.622 G ops/s at two (run r04v)
+static int launch_rounds(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
+{
+    const int64_t n = a.n;
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    if (p.engine == Engine::kValsOnePass) {
+        with_bool(p.il, [&](auto il) {
+            hipLaunchKernelGGL((k_lookup<1, decltype(il)::value>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a,
+                               (int64_t)0, n);
+        });
+        return hipGetLastError() == hipSuccess ? 0 : -3;
+    }
+    const int64_t head = p.lookup_head;
     hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((head + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, head);
     if (n > head) hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((n - head + 63) / 64)), dim3(256), 0, s, a, head, n);
-    if (a.ack_direct) {
+    int rc = 0;
+    if (p.engine == Engine::kRoundsAckDirect) {
         hipLaunchKernelGGL(k_ack_resolve, dim3(grid), dim3(256), 0, s, a);
-    } else if (a.inv_direct) {
+    } else if (p.engine == Engine::kRoundsInvDirect) {
         hipLaunchKernelGGL(k_inv_resolve, dim3(grid), dim3(256), 0, s, a, (int64_t)0, n);
-        if (bl.g.st_value == 31) hipLaunchKernelGGL((k_inv_commit<31>), dim3(grid), dim3(256), 0, s, a);
-        else if (bl.g.st_value == 287) hipLaunchKernelGGL((k_inv_commit<287>), dim3(grid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_inv_commit<0>), dim3(grid), dim3(256), 0, s, a);
+        with_sv(p.sv, [&](auto v) { hipLaunchKernelGGL((k_inv_commit<decltype(v)::value>), dim3(grid), dim3(256), 0, s, a); });
     } else {
-#define HKV_ROUNDS(T, V)                                                                          \
-    do {                                                                                          \
-        if (big && rlds > 64 * 1024 &&                                                            \
-            hipFuncSetAttribute((const void *)k_resolve0<T, V, 128>,                              \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds) != hipSuccess) \
-            return -3;                                                                            \
-        if (big && big_direct) hipLaunchKernelGGL((k_resolve0_direct<T, V>), dim3(grid), dim3(256), 0, s, a); \
-        else if (big) hipLaunchKernelGGL((k_resolve0<T, V, 128>), dim3(rgrid), dim3(128), rlds, s, a); \
-        else hipLaunchKernelGGL((k_resolve0<T, V, 256>), dim3(rgrid), dim3(256), rlds, s, a);     \
-        for (int r = 1; r <= a.rounds; ++r) {                                                     \
-            hipLaunchKernelGGL((k_cand<T>), dim3(cgrid), dim3(256), 0, s, a, r);                  \
-            hipLaunchKernelGGL((k_resolve<T, V>), dim3(grid), dim3(256), V == 31 ? 256 * bl.esz : 0, s, a, r); \
-        }                                                                                         \
-        hipLaunchKernelGGL((k_commit<V>), dim3(grid), dim3(256), 0, s, a);                         \
-        if (a.rounds > 0) hipLaunchKernelGGL((k_fb_exec<T, V>), dim3(256), dim3(kFbThreads), 0, s, a); \
-    } while (0)
-#define HKV_ROUNDS_SV(T)                                      \
-    do {                                                      \
-        if (bl.g.st_value == 31) HKV_ROUNDS(T, 31);           \
-        else if (bl.g.st_value == 287) HKV_ROUNDS(T, 287);    \
-        else HKV_ROUNDS(T, 0);                                \
-    } while (0)
-    switch (bl.type) {
-    case kLocal: HKV_ROUNDS_SV(kLocal); break;
-    case kLocalAfterMemb: HKV_ROUNDS_SV(kLocalAfterMemb); break;
-    case kInvs: HKV_ROUNDS_SV(kInvs); break;
-    case kAcks: HKV_ROUNDS_SV(kAcks); break;
-    default: HKV_ROUNDS_SV(kVals); break;
+        switch (a.type) {
+        case kLocal: rc = launch_rounds_t<kLocal>(a, p, s); break;
+        case kLocalAfterMemb: rc = launch_rounds_t<kLocalAfterMemb>(a, p, s); break;
+        case kInvs: rc = launch_rounds_t<kInvs>(a, p, s); break;
+        case kAcks: rc = launch_rounds_t<kAcks>(a, p, s); break;
+        default: rc = launch_rounds_t<kVals>(a, p, s); break;
+        }
     }
-#undef HKV_ROUNDS_SV
-#undef HKV_ROUNDS
+    if (rc) return rc;
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_batch(BatchLaunch &bl, hipStream_t s)
+{
+    if (bl.n <= 0) return 0;
+    const BatchPlan p = plan_batch(bl);
+    if (p.refuse) return p.refuse;
+    const BatchArgs a = make_args(bl, p);
+    if (p.patches == Patches::kApplyFirst)   // the patches as op writes first, then the launch as usual
+        hipLaunchKernelGGL(k_apply_patch, dim3((unsigned)((bl.n + 255) / 256)), dim3(256), 0, s, bl.elems, bl.patch, bl.n,
+                           bl.esz, bl.g.st_value);
+    int rc;
+    switch (p.engine) {
+    case Engine::kSmall: rc = launch_small(a, p, s); break;
+    case Engine::kLocalDirect: rc = launch_local(a, p, s); break;
+    case Engine::kRows:
+    case Engine::kUniqueLds64:
+    case Engine::kUniqueLdsBig:
+    case Engine::kUniqueInPlace: rc = launch_unique(a, p, s); break;
+    default: rc = launch_rounds(a, p, s); break;   // kValsOnePass and the rounds
     }
-    }
-    if (hipGetLastError() != hipSuccess) return -3;
-    if (bl.type == kInvs && bl.ns_idx && bl.node_suspected) {
+    if (rc) return rc;
+    if (p.node_suspected) {
         hipLaunchKernelGGL(k_node_suspected, dim3((bl.n_batches + 255) / 256), dim3(256), 0, s, bl.elems, bl.ns_idx,
                            bl.node_suspected, bl.n_batches, bl.stride, bl.esz, bl.offsets);
         if (hipGetLastError() != hipSuccess) return -4;

@@ -1,8 +1,10 @@
-// hkv_kernels.hip -- CDNA4 (gfx950) kernels of table setup: CityHash128 of key ids and populate.
+// hkv_kernels.hip -- CDNA4 (gfx950) kernels on the table itself: CityHash128 of key ids, populate, and the
+// inline residency's conversions (at the end).
 //
 // Populate (spacetime.c:32-68 / mica.c:78-146): hash every id, sort the inserts by bucket (stable,
 // so each bucket sees its inserts in insertion order), one owner lane per bucket replays the MICA
-// slot rules, and the log entries are written in parallel. The batch path is in hkv_batch.hip.
+// slot rules, and the log entries are written in parallel. The batch path is in hkv_batch.hip and
+// hkv_batch_small.hip.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
@@ -204,6 +206,53 @@ int launch_populate(const PopulateLaunch &pl, hipStream_t s)
         }
     }
     return 0;
+}
+
+// ------------------------------------------------------------------ the inline residency's conversions
+// Four lanes per bucket, 16 B each (two slots). The inline key is the one in the bucket's lowest in-use slot:
+// chosen from the bucket alone, so the same key whenever the conversion runs (nothing is inserted under the
+// rounds). to_inline copies the bucket into the first half of its line with that slot flagged and the key's
+// whole 64-B entry into the second half; to_log copies the second half back to the entry's log offset. An
+// empty bucket's line holds the (empty) bucket and no flag; its second half is never read.
+template <bool TO_INLINE>
+__global__ __launch_bounds__(256) void k_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line,
+                                                        uint64_t num_bkts, uint64_t log_mask)
+{
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    const uint64_t b = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+    const bool live = b < num_bkts;   // (the four lanes of a group share b: a group is live or idle as a whole)
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (live) v = reinterpret_cast<const uint4 *>(index + b * 64u)[q];
+    const uint64_t s0 = (uint64_t)v.x | ((uint64_t)v.y << 32), s1 = (uint64_t)v.z | ((uint64_t)v.w << 32);
+    const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
+    const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
+    uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
+#pragma unroll
+    for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+    const int first = o ? __ffs(o) - 1 : 0;
+    const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+    if (!live) return;
+    uint4 *ln = reinterpret_cast<uint4 *>(line + b * 128u);
+    uint4 *ent = reinterpret_cast<uint4 *>(log + (off & log_mask));
+    if (TO_INLINE) {
+        if (o && (first >> 1) == q) {
+            if (first & 1) v.w |= (uint32_t)(kInlineSlotBit >> 32);
+            else v.y |= (uint32_t)(kInlineSlotBit >> 32);
+        }
+        ln[q] = v;
+        ln[4 + q] = o ? ent[q] : make_uint4(0u, 0u, 0u, 0u);
+    } else if (o) {
+        ent[q] = ln[4 + q];
+    }
+}
+
+int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uint64_t num_bkts, uint64_t log_mask,
+                          bool to_inline, hipStream_t s)
+{
+    const unsigned grid = (unsigned)((num_bkts + 63) / 64);
+    if (to_inline) hipLaunchKernelGGL(k_layout_convert<true>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
+    else hipLaunchKernelGGL(k_layout_convert<false>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
 }  // namespace hkv

@@ -482,12 +482,8 @@ __device__ __forceinline__ void wave_ranks(const unsigned long long *b, int lane
 // so the op slab is read and written once per round (by that launch) instead of twice.
 // One wave per WPW workers: all their state loads, then all their trace loads, are in flight
 // together (a wave's work is two dependent loads; with WPW = 2 the 16384 workers of configs[1] fit
-// the chip's 8192 wave slots in one pass instead of two).
-#ifdef HKV_PLAN_NUM_SGPR
-#define HKV_PLAN_SGPR_ATTR __attribute__((amdgpu_num_sgpr(HKV_PLAN_NUM_SGPR)))
-#else
-#define HKV_PLAN_SGPR_ATTR
-#endif
+// the chip's 8192 wave slots in one pass instead of two). No SGPR attribute: a cap of 80 was within box noise
+// (runs r06f, r06x).
 struct PlanArgs {   // hkv_wl_refill_plan's arguments
     uint8_t *states;
     int32_t n_workers, stride;
@@ -594,7 +590,7 @@ __device__ __forceinline__ void refill_plan_body(const PlanArgs &pa, int bx)
 }
 
 template <int WPW>
-__global__ __launch_bounds__(256) HKV_PLAN_SGPR_ATTR void k_refill_plan_w(PlanArgs pa)
+__global__ __launch_bounds__(256) void k_refill_plan_w(PlanArgs pa)
 {
     refill_plan_body<WPW>(pa, blockIdx.x);
 }
@@ -1798,7 +1794,7 @@ __global__ __launch_bounds__(256) void k_peer_ts_at(PeerTsArgs pt) { peer_ts_at_
 // peers' slabs, reading the table) and are bound by dependent loads, so side by side in one grid they overlap
 // and the launch boundary between them goes. Blocks [0, plan_blocks) plan, the rest take timestamps.
 template <bool IL>
-__global__ __launch_bounds__(256) HKV_PLAN_SGPR_ATTR void k_plan_peer_ts(PlanArgs pa, PeerTsArgs pt, int plan_blocks)
+__global__ __launch_bounds__(256) void k_plan_peer_ts(PlanArgs pa, PeerTsArgs pt, int plan_blocks)
 {
     if ((int)blockIdx.x < plan_blocks) refill_plan_body<2>(pa, blockIdx.x);
     else peer_ts_at_body<IL>(pt, (int)blockIdx.x - plan_blocks);
@@ -2254,18 +2250,12 @@ int hkv_wl_refill_plan_peer_ts(uint8_t *states, int32_t n_workers, int32_t strid
                       patch};
     const PeerTsArgs pt{tv, invs, vals, phys, n, op_size, peer_ts, round};
     const int plan_blocks = (n_workers + 7) / 8;
-#ifdef HKV_PLAN_PTS_SPLIT   // (a build macro for A/B: the two launches of before)
-    hipLaunchKernelGGL(k_refill_plan_w<2>, dim3((unsigned)plan_blocks), dim3(256), 0, (hipStream_t)stream, pa);
-    if (n && tv.line) hipLaunchKernelGGL(k_peer_ts_at<true>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
-    else if (n) hipLaunchKernelGGL(k_peer_ts_at<false>, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)stream, pt);
-#else
     if (tv.line)
         hipLaunchKernelGGL(k_plan_peer_ts<true>, dim3((unsigned)plan_blocks + blocks_for(n)), dim3(256), 0,
                            (hipStream_t)stream, pa, pt, plan_blocks);
     else
         hipLaunchKernelGGL(k_plan_peer_ts<false>, dim3((unsigned)plan_blocks + blocks_for(n)), dim3(256), 0,
                            (hipStream_t)stream, pa, pt, plan_blocks);
-#endif
     return ok();
 }
 

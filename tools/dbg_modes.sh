@@ -8,9 +8,8 @@
 #   here:        tools/dbg_modes.sh build      (build_ab/libhermeskv_dbg.so)
 #   on the box:  TAG=dbg MODES="0 2 16" tools/dbg_modes.sh
 if [ "$1" = build ]; then
-  mkdir -p build_ab && cd hermes_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics \
-    -DHKV_DEBUG_MODES -shared -o ../../build_ab/libhermeskv_dbg.so hkv_batch.hip hkv_kernels.hip hkv_runtime.hip \
-    hkv_workload.hip hkv_hades.cpp
+  mkdir -p build_ab && make -s -C hermes_amd/csrc -j8 BUILD=../../build_ab/obj_dbg OUT=../../build_ab/libhermeskv_dbg.so \
+    EXTRA=-DHKV_DEBUG_MODES
   exit $?
 fi
 out=gpurun_out/${TAG:-dbg}; mkdir -p $out; export TMPDIR=/tmp
