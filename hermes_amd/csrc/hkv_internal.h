@@ -185,6 +185,13 @@ constexpr uint64_t kPhysInline = 1ull << 62;      // hkv_wl_peer_locate's offset
 // index + log -> lines (to_inline), or the inline entries back to their log offsets
 int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uint64_t num_bkts, uint64_t log_mask,
                           bool to_inline, hipStream_t s);
+// The table census (hermeskv.h "Table census and digest"): one pass over the buckets -- of `line` when it is
+// non-NULL (the table is INLINE), else of `index` -- into out[0 .. kCensusWords), which the launch zeroes first.
+// offender_keys (may be NULL) takes up to offender_cap keys of live keys that are not VALID.
+constexpr int kCensusWords = 25;   // sizeof(hkv_census) / 8
+int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                        uint64_t num_bkts, unsigned long long *out, unsigned long long *offender_keys,
+                        uint64_t offender_cap, int device, hipStream_t s);
 // whether launch_batch runs this launch on kernels that know the inline residency (bl.line aside)
 bool batch_inline_capable(const BatchLaunch &bl);
 

@@ -6,6 +6,7 @@
 // slot rules, and the log entries are written in parallel. The batch path is in hkv_batch.hip and
 // hkv_batch_small.hip.
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -252,6 +253,208 @@ int launch_layout_convert(const uint8_t *index, uint8_t *log, uint8_t *line, uin
     const unsigned grid = (unsigned)((num_bkts + 63) / 64);
     if (to_inline) hipLaunchKernelGGL(k_layout_convert<true>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
     else hipLaunchKernelGGL(k_layout_convert<false>, dim3(grid), dim3(256), 0, s, index, log, line, num_bkts, log_mask);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------ the table census
+// hermeskv.h "Table census and digest". A streaming pass over the buckets like the conversions: four lanes per
+// bucket, 16 B each, 64 buckets per block and step, a grid of a few blocks per CU striding over the table. IL
+// reads the 128-B lines (the bucket, and the inline key's entry from the line's second half -- its log entry
+// is stale), else the 64-B buckets; every other live slot's entry comes from the log, 64 B per step of the
+// lane group. A lane hashes the two words it holds of each 64 B (the position salt makes that independent of
+// the other lanes) and the group adds up. Lane 1 of a group holds state, op_buffer_index and timestamp (entry
+// words 2 and 3) and keeps the group's counts. Every count is reduced per wave by shuffles and per block through
+// LDS, then one atomic per field and block goes to memory: tens of thousands for the whole table, and sums,
+// xors and maxima only, so the result is the same bytes in whatever order they land.
+namespace {
+constexpr uint64_t kMixG = 0x9E3779B97F4A7C15ull;
+// word indices of hkv_census
+enum : int { kCsKeys = 0, kCsDead = 1, kCsState = 2, kCsObi = 10, kCsCid = 11, kCsMaxTs = 20, kCsSum = 21,
+             kCsXor = 22, kCsLines = 23, kCsOffenders = 24 };
+static_assert(kCsOffenders + 1 == kCensusWords, "hkv_census is kCensusWords 64-bit words");
+constexpr int kCensusBlock = 256;                 // threads: 64 buckets per step
+constexpr int kCensusBktsPerBlock = kCensusBlock / 4;
+
+__device__ __forceinline__ uint64_t mix64(uint64_t x)   // the splitmix64 finaliser
+{
+    x ^= x >> 30;
+    x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27;
+    x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return x;
+}
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+}  // namespace
+
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_census(const uint8_t *__restrict__ index,
+                                                               const uint8_t *__restrict__ log,
+                                                               const uint8_t *__restrict__ line, uint64_t num_bkts,
+                                                               uint64_t log_mask, uint64_t log_head, uint64_t log_cap,
+                                                               uint32_t chunks, unsigned long long *out,
+                                                               unsigned long long *offender_keys, uint64_t offender_cap)
+{
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3;
+    const uint64_t tiles = (num_bkts + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock;
+    uint32_t n_keys = 0, n_dead = 0, n_obi = 0, n_lines = 0, n_off = 0, n_state[6] = {0, 0, 0, 0, 0, 0},
+             n_cid[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t max_ts = 0, dsum = 0, dxor = 0;
+    // the masks of this lane's two words of an entry's first 64 B (words 2q and 2q + 1): key; state and ts cid,
+    // ts version; the value from byte 33 on
+    const uint64_t mask_a = q == 0 ? 0ull : q == 1 ? 0xFF00000000FF0000ull : q == 2 ? 0xFFFFFFFFFFFFFF00ull : ~0ull;
+    const uint64_t mask_b = q == 1 ? 0x00000000FFFFFFFFull : ~0ull;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
+        const uint64_t b = tile * kCensusBktsPerBlock + (threadIdx.x >> 2);
+        const bool live = b < num_bkts;   // (the four lanes of a group share b)
+        uint4 v = make_uint4(0u, 0u, 0u, 0u), iv = v;
+        if (live) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(IL ? line + b * 128u : index + b * 64u);
+            v = src[q];
+            if (IL) iv = src[4 + q];
+        }
+        const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
+        const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
+        const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
+        uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
+#pragma unroll
+        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+        while (o) {   // (group-uniform: the four lanes of a group stay together)
+            const int j = __ffs(o) - 1;
+            o &= o - 1;
+            uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
+            const bool il = IL && (off & kInlineOffBit);
+            if (IL) off &= ~kInlineOffBit;
+            if (log_head - off >= log_cap) {   // the lookup's window check: the log has overwritten the entry
+                ++n_dead;
+                continue;
+            }
+            const uint4 *ent = reinterpret_cast<const uint4 *>(log + (off & log_mask));
+            const uint4 c = il ? iv : ent[q];
+            const uint64_t wa = u64_of(c.x, c.y), wb = u64_of(c.z, c.w);
+            uint64_t e = mix64((wb & mask_b) + (uint64_t)(2 * q + 2) * kMixG);
+            if (q) e += mix64((wa & mask_a) + (uint64_t)(2 * q + 1) * kMixG);   // (word 0 is skipped)
+            if (BIG) {
+                for (uint32_t k = 1; k < chunks; ++k) {
+                    const uint4 d = ent[4 * k + q];
+                    const uint64_t i = 8ull * k + 2u * q;
+                    e += mix64(u64_of(d.x, d.y) + (i + 1) * kMixG) + mix64(u64_of(d.z, d.w) + (i + 2) * kMixG);
+                }
+            }
+            e += __shfl_xor(e, 1, 4);
+            e += __shfl_xor(e, 2, 4);
+            const uint64_t h = mix64(e);
+            const uint64_t key = __shfl(wb, 0, 4);
+            // lane 1: wa = entry bytes 16..23, wb = 24..31
+            const uint32_t state = (uint32_t)(wa >> 16) & 0xFFu, obi = (uint32_t)(wa >> 40) & 0xFFu,
+                           cid = (uint32_t)(wa >> 56);
+            const uint64_t ts = ((wb & 0xFFFFFFFFull) << 8) | cid;
+            const bool not_valid = state != kValid;
+            const uint32_t si = state >= 1 && state <= 5 ? state : 0, ci = cid < 8 ? cid : 8;
+            ++n_keys;
+            n_lines += il;
+            n_obi += obi != kObiEmpty;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) n_state[k] += si == (uint32_t)k;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) n_cid[k] += not_valid && ci == (uint32_t)k;
+            max_ts = ts > max_ts ? ts : max_ts;
+            dsum += h;
+            dxor ^= mix64(h + kMixG);
+            if (offender_keys) {   // (uniform) one returning atomic per wave and step that found offenders
+                const bool mine = q == 1 && not_valid;
+                const unsigned long long m = __ballot(mine);
+                if (m) {
+                    const int leader = __ffsll(m) - 1;
+                    unsigned long long base = 0;
+                    if (lane == leader) base = atomicAdd(&out[kCsOffenders], (unsigned long long)__popcll(m));
+                    base = __shfl(base, leader);
+                    const uint64_t pos = base + (uint64_t)__popcll(m & ((1ull << lane) - 1));
+                    if (mine && pos < offender_cap) offender_keys[pos] = key;
+                }
+            } else {
+                n_off += not_valid;
+            }
+        }
+    }
+    // only lane 1 of a group read the meta: its counts are the group's
+    unsigned long long r[kCensusWords];
+#pragma unroll
+    for (int k = 0; k < kCensusWords; ++k) r[k] = 0;
+    if (q == 1) {
+        r[kCsKeys] = n_keys;
+        r[kCsDead] = n_dead;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) r[kCsState + k] = n_state[k];
+        r[kCsObi] = n_obi;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) r[kCsCid + k] = n_cid[k];
+        r[kCsMaxTs] = max_ts;
+        r[kCsSum] = dsum;
+        r[kCsXor] = dxor;
+        r[kCsLines] = n_lines;
+        r[kCsOffenders] = n_off;
+    }
+    __shared__ unsigned long long sh[kCensusBlock / 64][kCensusWords];
+#pragma unroll
+    for (int k = 0; k < kCensusWords; ++k) {
+        unsigned long long x = r[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const unsigned long long y = __shfl_xor(x, d);
+            x = k == kCsMaxTs ? (y > x ? y : x) : k == kCsXor ? x ^ y : x + y;
+        }
+        if (lane == 0) sh[threadIdx.x >> 6][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCensusWords) {
+        const int k = threadIdx.x;
+        unsigned long long x = sh[0][k];
+        for (int w = 1; w < kCensusBlock / 64; ++w) {
+            const unsigned long long y = sh[w][k];
+            x = k == kCsMaxTs ? (y > x ? y : x) : k == kCsXor ? x ^ y : x + y;
+        }
+        if (x) {   // (0 is neutral for all three)
+            if (k == kCsMaxTs) atomicMax(&out[k], x);
+            else if (k == kCsXor) atomicXor(&out[k], x);
+            else atomicAdd(&out[k], x);
+        }
+    }
+}
+
+int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                        uint64_t num_bkts, unsigned long long *out, unsigned long long *offender_keys,
+                        uint64_t offender_cap, int device, hipStream_t s)
+{
+    if (g.entry_size % 64 || (line && g.entry_size != 64)) return -1;
+    if (hipMemsetAsync(out, 0, kCensusWords * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    const uint32_t chunks = g.entry_size / 64;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    // A persistent grid striding over the table: as many blocks per CU as the instance's registers let the CU
+    // hold at once, so the blocks all start together and end together (a grid that needs a second, partial
+    // round of blocks ends with idle CUs). HKV_CENSUS_BLOCKS_PER_CU overrides it (timing experiments); no block
+    // waits for another, so any grid gives the same result.
+    static const int env_bpc = getenv("HKV_CENSUS_BLOCKS_PER_CU") ? atoi(getenv("HKV_CENSUS_BLOCKS_PER_CU")) : 0;
+    int bpc = env_bpc;
+    if (bpc <= 0) {
+        const void *fn = line ? (const void *)k_table_census<true, false>
+                       : chunks > 1 ? (const void *)k_table_census<false, true> : (const void *)k_table_census<false, false>;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kCensusBlock, 0) != hipSuccess || bpc <= 0) bpc = 4;
+    }
+    if (bpc > 8) bpc = 8;
+    const uint64_t tiles = (num_bkts + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock, cap = (uint64_t)cus * bpc;
+    const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kCensusBlock);
+    if (!offender_cap) offender_keys = nullptr;
+    if (line)
+        hipLaunchKernelGGL((k_table_census<true, false>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
+                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
+    else if (chunks > 1)
+        hipLaunchKernelGGL((k_table_census<false, true>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
+                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
+    else
+        hipLaunchKernelGGL((k_table_census<false, false>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
+                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

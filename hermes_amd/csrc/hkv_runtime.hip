@@ -135,6 +135,7 @@ struct hkv_table {
     int layout_pref = HKV_LAYOUT_LOG, layout_state = HKV_LAYOUT_LOG;
     uint64_t conversions = 0, inline_launches = 0;
     hipStream_t last_stream = nullptr;   // the stream of the table's last launch or conversion
+    hkv_census *d_census = nullptr;      // hkv_table_census's device buffer, allocated by its first call
     unsigned long long *d_evictions = nullptr;
     int64_t inserted = 0;
     uint32_t skip_key = 0;
@@ -463,6 +464,7 @@ int hkv_table_destroy(hkv_table *t)
     hipFree(t->d_index);
     hipFree(t->d_log);
     hipFree(t->d_line);
+    hipFree(t->d_census);
     hipFree(t->d_evictions);
     hipFree(t->d_batch);
     hipFree(t->d_fw);
@@ -853,6 +855,47 @@ int hkv_copy_lines(hkv_table *t, void *dst, uint64_t off, uint64_t bytes)
     HIP_TRY(hipStreamSynchronize(t->stream));
     HIP_TRY(hipStreamSynchronize(t->last_stream));
     HIP_TRY(hipMemcpy(dst, t->d_line + off, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// The census reads the table as it is: the lines while INLINE, index and log while LOG. It is no launch and no
+// export in the sense of the layout rules -- it converts nothing and leaves `conversions` and `inline_launches`
+// alone -- but it is ordered like one: after the table's last stream, which it then becomes.
+static_assert(sizeof(hkv_census) == kCensusWords * 8, "hkv_census and the kernel's word indices");
+uint32_t hkv_census_bytes(void) { return (uint32_t)sizeof(hkv_census); }
+
+int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender_keys, uint64_t offender_cap,
+                           void *stream)
+{
+    if (!t || !d_out) return fail(-1, "null argument");
+    if ((uintptr_t)d_out & 7) return fail(-1, "d_out must be 8-byte aligned");
+    if (offender_cap && !d_offender_keys) return fail(-1, "offender_cap without d_offender_keys");
+    srv_stop(t);   // the serving kernel of the host-pointer path writes the table outside every stream order
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);   // against hkv_table_populate (geo.log_head)
+    HIP_TRY(hipSetDevice(t->cfg.device));
+    if (t->last_stream != s) HIP_TRY(hipStreamSynchronize(t->last_stream));
+    if (t->stream != s) HIP_TRY(hipStreamSynchronize(t->stream));   // the host-pointer path's launches
+    const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
+    if (int rc = launch_table_census(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr, t->cfg.num_bkts,
+                                     reinterpret_cast<unsigned long long *>(d_out),
+                                     reinterpret_cast<unsigned long long *>(d_offender_keys), offender_cap,
+                                     t->cfg.device, s))
+        return fail(-3, "census launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    t->last_stream = s;
+    TRACE("census (%s)", inl ? "INLINE" : "LOG");
+    return 0;
+}
+
+int hkv_table_census(hkv_table *t, hkv_census *host_out)
+{
+    if (!t || !host_out) return fail(-1, "null argument");
+    HIP_TRY(hipSetDevice(t->cfg.device));
+    if (!t->d_census) HIP_TRY(hipMalloc(&t->d_census, sizeof(hkv_census)));   // kept until hkv_table_destroy
+    hipStream_t s = t->last_stream;
+    if (int rc = hkv_table_census_async(t, t->d_census, nullptr, 0, s)) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(host_out, t->d_census, sizeof(hkv_census), hipMemcpyDeviceToHost));
     return 0;
 }
 

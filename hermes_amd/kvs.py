@@ -11,12 +11,13 @@ Two ways in, matching the two halves of include/hermeskv.h:
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 import numpy as np
 import torch
 
 from . import layout as L
-from .lib import ABI_VERSION, HkvBatchDesc, HkvConfig, HkvLayoutInfo, Membership, check, raw
+from .lib import ABI_VERSION, HkvBatchDesc, HkvCensus, HkvConfig, HkvLayoutInfo, Membership, check, raw
 
 _L = raw()
 
@@ -90,6 +91,47 @@ BATCH_SMALL = 2    # the single-workgroup kernel (launches of at most 4096 eleme
 BATCH_PACKED = 4   # INV / VAL batches back to back, d_counts = n_batches + 1 offsets
 BATCH_UNIQUE = 8   # no key twice in the launch (INV batches: one pass)
 BATCH_ROWS = 16    # with BATCH_UNIQUE: rows of one layout, element j of every row on one key
+
+
+CENSUS_WORDS = ctypes.sizeof(HkvCensus) // 8
+# hkv_census's fields as (first word, words) of its 64-bit words
+CENSUS_FIELDS = {name: (getattr(HkvCensus, name).offset // 8, getattr(HkvCensus, name).size // 8)
+                 for name, _ in HkvCensus._fields_}
+
+
+def _census_dict(raw: bytes) -> dict:
+    w = np.frombuffer(raw, dtype="<u8")
+    return {name: int(w[a]) if n == 1 else [int(x) for x in w[a:a + n]] for name, (a, n) in CENSUS_FIELDS.items()}
+
+
+@dataclasses.dataclass
+class Census:
+    """The result of HermesKV.census(), still on the device. `tensor`: hkv_census's CENSUS_WORDS 64-bit words as
+    int64 (the unsigned words' bit patterns), `offender_keys`: the key list, or None. Nothing is read back until
+    asked: field(name) is a device view for code that stays on the stream (a collective, a comparison), host()
+    and the attributes named like hkv_census's fields (keys, by_state, digest_sum, ...) synchronise and return
+    Python integers."""
+    tensor: torch.Tensor
+    offender_keys: torch.Tensor | None = None
+
+    def field(self, name: str) -> torch.Tensor:
+        a, n = CENSUS_FIELDS[name]
+        return self.tensor[a:a + n]
+
+    def host(self) -> dict:
+        return _census_dict(self.tensor.cpu().numpy().tobytes())
+
+    def __getattr__(self, name: str):
+        if name in CENSUS_FIELDS:
+            return self.host()[name]
+        raise AttributeError(name)
+
+    def offenders_host(self) -> np.ndarray:
+        """the listed keys (uint64), min(offenders, the list's capacity) of them, in no particular order"""
+        if self.offender_keys is None:
+            return np.empty(0, np.uint64)
+        n = min(self.host()["offenders"], self.offender_keys.numel())
+        return self.offender_keys[:n].cpu().numpy().view(np.uint64)
 
 
 class HermesKV:
@@ -370,6 +412,35 @@ class HermesKV:
         out = np.empty(nbytes, dtype=np.uint8)
         check(_L.hkv_copy_lines(self.h, out.ctypes.data_as(ctypes.c_void_p), offset, nbytes), "hkv_copy_lines")
         return out
+
+    # -- census (include/hermeskv.h, "Table census and digest")
+    def census(self, stream: torch.cuda.Stream | None = None, offender_cap: int = 0,
+               out: torch.Tensor | None = None, offender_keys: torch.Tensor | None = None) -> "Census":
+        """hkv_table_census_async: the table's protocol state and digest, read in one pass from whichever
+        residency the table is in (nothing is converted or exported), asynchronously on `stream` (default:
+        torch's current). offender_cap: also list the keys of up to that many live keys that are not VALID.
+        out / offender_keys: int64 device tensors to write into (CENSUS_WORDS words, overwritten; offender_cap
+        keys or more, of which only the first min(offenders, offender_cap) are written) instead of new ones."""
+        dev = torch.device("cuda", self.device)
+        if out is None:
+            out = torch.empty(CENSUS_WORDS, dtype=torch.int64, device=dev)
+        assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= CENSUS_WORDS
+        if offender_keys is None and offender_cap:
+            offender_keys = torch.zeros(int(offender_cap), dtype=torch.int64, device=dev)
+        if offender_keys is not None:
+            assert offender_keys.is_cuda and offender_keys.dtype == torch.int64 and offender_keys.is_contiguous()
+            assert offender_keys.numel() >= offender_cap
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_census_async(self.h, ctypes.c_void_p(out.data_ptr()),
+                                        ctypes.c_void_p(offender_keys.data_ptr()) if offender_cap else None,
+                                        int(offender_cap), ctypes.c_void_p(s)), "hkv_table_census_async")
+        return Census(out[:CENSUS_WORDS], offender_keys[:offender_cap] if offender_cap else None)
+
+    def census_host(self) -> dict:
+        """hkv_table_census: the same, synchronous, as a dict (no offender list)"""
+        v = HkvCensus()
+        check(_L.hkv_table_census(self.h, ctypes.byref(v)), "hkv_table_census")
+        return _census_dict(bytes(v))
 
     def device_index(self) -> int:
         return _L.hkv_device_index(self.h)

@@ -50,6 +50,14 @@ class HkvLayoutInfo(ctypes.Structure):
                 ("line_bytes", ctypes.c_uint64)]
 
 
+class HkvCensus(ctypes.Structure):
+    """hkv_census (include/hermeskv.h, "Table census and digest"): 25 64-bit words"""
+    _fields_ = [("keys", ctypes.c_uint64), ("dead_slots", ctypes.c_uint64), ("by_state", ctypes.c_uint64 * 8),
+                ("obi_set", ctypes.c_uint64), ("not_valid_by_cid", ctypes.c_uint64 * 9), ("max_ts", ctypes.c_uint64),
+                ("digest_sum", ctypes.c_uint64), ("digest_xor", ctypes.c_uint64), ("from_lines", ctypes.c_uint64),
+                ("offenders", ctypes.c_uint64)]
+
+
 class Membership(ctypes.Structure):
     """spacetime_group_membership (8 bytes) by value. Declared as one 64-bit field: the SysV
     x86-64 ABI classifies both as a single INTEGER eightbyte, and libffi handles a scalar
@@ -83,6 +91,9 @@ _L.hkv_table_prefer_layout.argtypes = [_P, ctypes.c_int]
 _L.hkv_table_layout.argtypes = [_P, ctypes.POINTER(HkvLayoutInfo)]
 _L.hkv_table_apply_layout.argtypes = [_P, _P]
 _L.hkv_copy_lines.argtypes = [_P, _P, ctypes.c_uint64, ctypes.c_uint64]
+_L.hkv_census_bytes.restype = ctypes.c_uint32
+_L.hkv_table_census_async.argtypes = [_P, _P, _P, ctypes.c_uint64, _P]
+_L.hkv_table_census.argtypes = [_P, ctypes.POINTER(HkvCensus)]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

@@ -694,6 +694,42 @@ class ReplicaGroupRound:
         return self.r.stats()
 
 
+def census_row(census) -> torch.Tensor:
+    """What a replica contributes to a group census, on the device: (digest_sum, digest_xor, keys, keys that
+    are not VALID) as int64 (the unsigned words' bit patterns), made from HermesKV.census() without a host
+    read."""
+    from .kvs import CENSUS_FIELDS
+    t = census.tensor
+    w = {n: CENSUS_FIELDS[n][0] for n in ("digest_sum", "digest_xor", "keys", "by_state")}
+    keys = t[w["keys"]]
+    return torch.stack([t[w["digest_sum"]], t[w["digest_xor"]], keys, keys - t[w["by_state"] + int(L.State.VALID)]])
+
+
+def census_rows_agree(rows: list, live_ranks) -> bool:
+    """whether every live rank's (digest_sum, digest_xor, keys) is the same"""
+    live = [tuple(rows[r][:3]) for r in live_ranks]
+    return all(x == live[0] for x in live)
+
+
+def group_census(kvs: HermesKV, group=None, live_ranks=None) -> dict:
+    """Whether the live replicas of a group hold the same table: every rank takes the census of its own table
+    (HermesKV.census: in place, from whichever residency the table is in) and one all_gather_into_tensor moves
+    census_row() of every rank, on torch's current stream and with no host read before it (gloo takes the CUDA
+    tensors as NCCL / RCCL does). Collective: every rank of `group` calls it, a failed one too (its row is
+    gathered and left out of the comparison by live_ranks, default: all ranks). Returns the same on every rank:
+    rows[r] = [digest_sum, digest_xor, keys, not VALID] of rank r as unsigned integers, live_ranks,
+    live_ranks_agree (digest and key count equal on all live ranks) and not_valid (rows' last column)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    row = census_row(kvs.census())
+    out = torch.empty(world * row.numel(), dtype=torch.int64, device=row.device)
+    dist.all_gather_into_tensor(out, row, group=group)
+    rows = [[int(x) & 0xFFFFFFFFFFFFFFFF for x in r] for r in out.view(world, -1).cpu().tolist()]
+    live = list(range(world)) if live_ranks is None else [int(r) for r in live_ranks]
+    return {"rows": rows, "live_ranks": live, "live_ranks_agree": census_rows_agree(rows, live),
+            "not_valid": [r[3] for r in rows]}
+
+
 class LoopbackGroup:
     """N replicas driven phase by phase in one process; the collectives are tensor copies with
     exactly the layouts the RCCL driver produces (all-gather: row p = rank p's slab;

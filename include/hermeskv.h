@@ -288,6 +288,54 @@ int  hkv_table_apply_layout(hkv_table *t, void *stream);
  * flag), in the manner of hkv_copy_index; does not convert. An error while the residency is not allocated. */
 int  hkv_copy_lines(hkv_table *t, void *host_dst, uint64_t offset, uint64_t bytes);
 
+/* Table census and digest. One streaming pass over the buckets that reports the table's protocol state: how
+ * many keys it holds, in which states, who wrote the ones that are not VALID, the highest timestamp, and a
+ * digest of every key's replicated bytes. It reads the table as it is, from whichever residency it is in (a LOG
+ * table from index and log, an INLINE table from the lines and, for the keys that are not inline, the log): it
+ * converts nothing, and the layout counters (conversions, inline_launches) do not move.
+ *
+ * A slot is live when it is in use and log_head - offset < log_cap (the lookup's window check); its entry is a
+ * live key. Every field is a sum, an xor or a maximum over the live keys, so the result does not depend on the
+ * order of buckets, blocks or atomics: equal tables give equal bytes.
+ *
+ * The digest, keyed by key (not by log position or bucket), with all arithmetic modulo 2^64:
+ *   mix64(x): x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31
+ *             (the splitmix64 finaliser)
+ *   G = 0x9E3779B97F4A7C15
+ *   An entry of E bytes (64, or 320 with big objects) is E/8 little-endian 64-bit words w[i]. Keep bytes 8..15
+ *   (key), 18 (state), 23 (ts cid), 24..27 (ts version) and 33..33+ST_VALUE_SIZE-1 (value, which ends with the
+ *   entry), zero every other byte: the masked words m[i]. m[0] is always zero and is skipped.
+ *   e = sum over i >= 1 of mix64(m[i] + (i + 1) * G)
+ *   h = mix64(e)
+ *   digest_sum = sum over the live keys of h;  digest_xor = xor over the live keys of mix64(h + G)
+ * Left out on purpose, being each replica's own: key_first, opcode, val_len, ack_bv, rmw_lwid,
+ * op_buffer_index, the lock byte (some engines keep launch tags there between launches, which is also why no
+ * "locked" count is offered) and the last-local-write timestamp. Two replicas that hold every key with the same
+ * state, timestamp and value have the same digest however their logs were filled. */
+typedef struct hkv_census {
+    uint64_t keys;               /* live slots: in-use, and log_head - offset < log_cap (the lookup's window check) */
+    uint64_t dead_slots;         /* in-use slots whose entry the log has overwritten */
+    uint64_t by_state[8];        /* live keys by state byte 1..5 (hermes_states_t); any other value counts in [0] */
+    uint64_t obi_set;            /* live keys with op_buffer_index != 255 */
+    uint64_t not_valid_by_cid[9];/* live keys not VALID, by ts cid 0..7; [8] = any other cid */
+    uint64_t max_ts;             /* max over live keys of (version << 8 | cid) */
+    uint64_t digest_sum, digest_xor;
+    uint64_t from_lines;         /* live keys whose entry was read from the inline residency (0 while LOG) */
+    uint64_t offenders;          /* live keys not VALID (= what the list below would hold with room for all) */
+} hkv_census;
+uint32_t hkv_census_bytes(void);   /* sizeof(hkv_census), for bindings */
+
+/* asynchronous on stream; d_out: device memory, sizeof(hkv_census), 8-byte aligned, overwritten (not
+ * accumulated). d_offender_keys (may be NULL): receives the 8-byte keys of up to offender_cap live keys that are
+ * not VALID, in no particular order; entries past min(offenders, offender_cap) are not written. Ordered after
+ * the launches already enqueued on the table's last stream; like a launch, one caller at a time per table. A
+ * serving kernel of the host-pointer path that is live on the table is stopped first, as by the other hkv_*
+ * calls. */
+int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender_keys,
+                           uint64_t offender_cap, void *stream);
+/* the same, synchronous, into host memory, no offender list */
+int hkv_table_census(hkv_table *t, hkv_census *host_out);
+
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
 hkv_table *hkv_default_table(void);
