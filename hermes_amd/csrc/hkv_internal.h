@@ -192,6 +192,17 @@ constexpr int kCensusWords = 25;   // sizeof(hkv_census) / 8
 int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
                         uint64_t num_bkts, unsigned long long *out, unsigned long long *offender_keys,
                         uint64_t offender_cap, int device, hipStream_t s);
+// Replica repair (hermeskv.h "Replica repair"). Extract: one pass like the census over the buckets [bkt_lo, bkt_hi)
+// -- of `line` when it is non-NULL, else of `index` -- that writes the masked entry image of every live slot whose
+// timestamp is at least min_ts to records (compacted, at most record_cap of them) and counts into
+// result[0] (records) and result[1] (scanned keys), which the launch zeroes first.
+int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                         uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *records, uint64_t record_cap,
+                         unsigned long long *result, int device, hipStream_t s);
+// Install: n records, no key twice, applied as an INV and (source VALID) a VAL each to the entries of `log`, or,
+// with `line` non-NULL, to the lines for the inline keys; result[0..3] (raised, equal, older, missed) zeroed first.
+int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,
+                         uint64_t n, unsigned long long *result, hipStream_t s);
 // whether launch_batch runs this launch on kernels that know the inline residency (bl.line aside)
 bool batch_inline_capable(const BatchLaunch &bl);
 

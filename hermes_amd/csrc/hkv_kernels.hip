@@ -1,5 +1,5 @@
-// hkv_kernels.hip -- CDNA4 (gfx950) kernels on the table itself: CityHash128 of key ids, populate, and the
-// inline residency's conversions (at the end).
+// hkv_kernels.hip -- CDNA4 (gfx950) kernels on the table itself: CityHash128 of key ids, populate, and (at the
+// end) the inline residency's conversions, the table census and the replica repair's extract and install.
 //
 // Populate (spacetime.c:32-68 / mica.c:78-146): hash every id, sort the inserts by bucket (stable,
 // so each bucket sees its inserts in insertion order), one owner lane per bucket replays the MICA
@@ -455,6 +455,314 @@ int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *
     else
         hipLaunchKernelGGL((k_table_census<false, false>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
                            g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------ replica repair: extract and install
+// hermeskv.h "Replica repair". A record is the entry image under the digest's mask, so both kernels move entries
+// as the 16-B chunks the census reads: lane q of a group of four holds bytes 16q..16q+15 of an entry's first 64 B
+// (q = 1: the meta -- state, ts cid, ts version; q = 2, 3: the value from byte 33 on), and a 320-B entry's other
+// 256 B are value only.
+namespace {
+// N per-thread counts -> out[0..N): per wave by shuffles, per block through LDS, one atomic per non-zero field and
+// block. Every thread of the block calls it.
+template <int N>
+__device__ __forceinline__ void block_add(const uint32_t (&c)[N], unsigned long long *out)
+{
+    __shared__ unsigned long long sh[kCensusBlock / 64][N];
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        unsigned long long x = c[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+        if (lane == 0) sh[threadIdx.x >> 6][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        unsigned long long x = 0;
+        for (int w = 0; w < kCensusBlock / 64; ++w) x += sh[w][threadIdx.x];
+        if (x) atomicAdd(&out[threadIdx.x], x);
+    }
+}
+}  // namespace
+
+// The census's pass over the buckets [bkt_lo, bkt_hi): every live slot whose timestamp is at least min_ts leaves
+// as one record. A block step takes kExtractK buckets per group of four lanes (512 per block) in three parts:
+// count (which slots qualify -- from the buckets alone when min_ts is 0, else with each entry's meta), reserve
+// (a prefix sum over the block and ONE returning atomic on the record counter, result[0]), write (each record as
+// whole 64-B runs, 16 B per lane, the mask applied in registers; nothing at or past record_cap). One atomic per
+// wave and step, as the census's offender list takes, was measured first: every one of them lands on the same
+// address, about 25M of them for 100M keys, and the extract took 258 ms (profiles/repair_100m.txt).
+constexpr int kExtractK = 8;
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *__restrict__ index,
+                                                                const uint8_t *__restrict__ log,
+                                                                const uint8_t *__restrict__ line, uint64_t bkt_lo,
+                                                                uint64_t bkt_hi, uint64_t log_mask, uint64_t log_head,
+                                                                uint64_t log_cap, uint32_t chunks, uint64_t min_ts,
+                                                                uint4 *__restrict__ records, uint64_t record_cap,
+                                                                unsigned long long *result)
+{
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3, wave = threadIdx.x >> 6;
+    constexpr uint64_t kSuper = (uint64_t)kCensusBktsPerBlock * kExtractK;   // buckets of one block step
+    const uint64_t tiles = (bkt_hi - bkt_lo + kSuper - 1) / kSuper;
+    __shared__ unsigned long long s_wtot[kCensusBlock / 64], s_base;
+    uint32_t n_scanned[1] = {0};
+    // the digest's mask on this lane's two words of an entry's first 64 B (as in k_table_census)
+    const uint64_t mask_a = q == 0 ? 0ull : q == 1 ? 0xFF00000000FF0000ull : q == 2 ? 0xFFFFFFFFFFFFFF00ull : ~0ull;
+    const uint64_t mask_b = q == 1 ? 0x00000000FFFFFFFFull : ~0ull;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
+        const uint64_t b0 = bkt_lo + tile * kSuper + (threadIdx.x >> 2);   // (the four lanes of a group share it)
+        // count: which slots of the group's kExtractK buckets leave as records (bit 8k + j: slot j of bucket k)
+        uint4 v[kExtractK];
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            v[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (b < bkt_hi) v[k] = reinterpret_cast<const uint4 *>(IL ? line + b * 128u : index + b * 64u)[q];
+        }
+        uint64_t qm = 0;
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
+            const uint64_t o0 = (s0 >> 24) & ~(IL ? kInlineOffBit : 0ull), o1 = (s1 >> 24) & ~(IL ? kInlineOffBit : 0ull);
+            // in use and inside the log window (the lookup's check); an idle group's words are zero
+            const uint32_t g0 = (uint32_t)(__ballot((s0 & 1u) && log_head - o0 < log_cap) >> gbase) & 0xFu;
+            const uint32_t g1 = (uint32_t)(__ballot((s1 & 1u) && log_head - o1 < log_cap) >> gbase) & 0xFu;
+            uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is live
+#pragma unroll
+            for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+            if (q == 0) n_scanned[0] += __popc(o);
+            if (min_ts) {   // (uniform) the filter needs each entry's timestamp: its bytes 16..31, the same for the four lanes
+                uint32_t left = o;
+                while (left) {   // (group-uniform)
+                    const int j = __ffs(left) - 1;
+                    left &= left - 1;
+                    const uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
+                    const uint4 m = (IL && (off & kInlineOffBit))
+                                        ? reinterpret_cast<const uint4 *>(line + b * 128u + 64u)[1]
+                                        : reinterpret_cast<const uint4 *>(log + ((off & ~(IL ? kInlineOffBit : 0ull)) & log_mask))[1];
+                    if ((((uint64_t)m.z << 8) | (m.y >> 24)) < min_ts) o &= ~(1u << j);
+                }
+            }
+            qm |= (uint64_t)o << (8 * k);
+        }
+        // reserve: the groups' counts scanned over the wave by shuffles and over the block through LDS, then one
+        // returning atomic on the record counter per block and step
+        const uint32_t cnt = (uint32_t)__popcll(qm);
+        uint32_t x = q == 0 ? cnt : 0u;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        const uint32_t excl = (uint32_t)__shfl(x, 0, 4) - cnt;   // records of the wave's groups before this one
+        const uint32_t wtot = (uint32_t)__shfl(x, 63);
+        if (lane == 0) s_wtot[wave] = wtot;
+        __syncthreads();
+        uint64_t before = excl, total = 0;
+#pragma unroll
+        for (int w = 0; w < kCensusBlock / 64; ++w) {
+            const uint64_t t = s_wtot[w];
+            if (w < wave) before += t;
+            total += t;
+        }
+        if (threadIdx.x == 0) s_base = total ? atomicAdd(&result[0], (unsigned long long)total) : 0ull;
+        __syncthreads();
+        uint64_t pos = s_base + before;   // (group-uniform) this group's first record
+        // write: a group writes each record as whole 64-B runs, 16 B per lane, the mask applied in registers
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
+            uint32_t m8 = (uint32_t)(qm >> (8 * k)) & 0xFFu;
+            while (m8) {   // (group-uniform)
+                const int j = __ffs(m8) - 1;
+                m8 &= m8 - 1;
+                const uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
+                const uint4 *ent = (IL && (off & kInlineOffBit))
+                                       ? reinterpret_cast<const uint4 *>(line + b * 128u + 64u)
+                                       : reinterpret_cast<const uint4 *>(log + ((off & ~(IL ? kInlineOffBit : 0ull)) & log_mask));
+                if (pos < record_cap) {
+                    const uint4 c = ent[q];
+                    const uint64_t wa = u64_of(c.x, c.y) & mask_a, wb = u64_of(c.z, c.w) & mask_b;
+                    uint4 *dst = records + pos * (4ull * chunks);
+                    dst[q] = make_uint4((uint32_t)wa, (uint32_t)(wa >> 32), (uint32_t)wb, (uint32_t)(wb >> 32));
+                    if (BIG)
+                        for (uint32_t kk = 1; kk < chunks; ++kk) dst[4 * kk + q] = ent[4 * kk + q];
+                }
+                ++pos;
+            }
+        }
+    }
+    block_add<1>(n_scanned, result + 1);
+}
+
+// One record per group of four lanes, one pass: the lanes load the record's first 64 B and look its key up as
+// the reference does (first in-use tag match, window check, 8-byte key compare; IL: in the bucket's line, whose
+// second half is the inline key's entry -- its log copy is neither read nor written). Lane 1 holds the entry's
+// meta and the record's and decides: hermes_exec_inv of an INV with the record's timestamp, value and sender =
+// ts cid, RMW flag 0 (on a table without RMWs), then hermes_exec_val when the record is VALID. The lanes write
+// back only the 16-B chunks of bytes 16..63 that changed; the lock byte, ack_bv, op buffer index and last-local-
+// write timestamp go back as they were read. A 320-B entry's other 256 value bytes move 64 consecutive bytes
+// per group and instruction. No key occurs twice, so no two groups share an entry.
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *__restrict__ index, uint8_t *log,
+                                                                uint8_t *line, const uint4 *__restrict__ records,
+                                                                uint64_t n, uint64_t bkt_mask, uint64_t log_mask,
+                                                                uint64_t log_head, uint64_t log_cap,
+                                                                uint32_t kvs_value, uint32_t chunks,
+                                                                unsigned long long *result)
+{
+    const uint64_t E4 = BIG ? 4ull * chunks : 4ull;   // 16-B chunks of a record
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    uint32_t cnt[4] = {0, 0, 0, 0};   // raised, equal, older, missed: lane 1 of a group counts for it
+    // a persistent grid striding over the records: the counts stay in registers until the block's end (one block
+    // per 64 records, each ending in its own atomics on the four result words, measured 19 ms for 100M records)
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kCensusBktsPerBlock; i0 < n;
+         i0 += (uint64_t)gridDim.x * kCensusBktsPerBlock) {   // (block-uniform)
+        const uint64_t i = i0 + (threadIdx.x >> 2);
+        const bool live = i < n;   // (the four lanes of a group share i)
+        uint4 r = make_uint4(0u, 0u, 0u, 0u);
+        if (live) r = records[i * E4 + q];
+        const uint64_t key = __shfl(u64_of(r.z, r.w), 0, 4);
+        const uint64_t bkt = (key & 0xFFFFFFFFFFFFull) & bkt_mask;
+        uint4 v = make_uint4(0u, 0u, 0u, 0u), ev = v;
+        if (live) {
+            const uint4 *src = reinterpret_cast<const uint4 *>(IL ? line + bkt * 128u : index + bkt * 64u);
+            v = src[q];
+            if (IL) ev = src[4 + q];
+        }
+        const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
+        const uint32_t tag = (uint32_t)(key >> 48);
+        const bool mt0 = live && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
+        const bool mt1 = live && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
+        const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu;
+        const uint32_t g1 = (uint32_t)(__ballot(mt1) >> gbase) & 0xFu;
+        uint32_t o = 0;   // bit 2*l + j: slot 2*l + j matches
+#pragma unroll
+        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+        const int first = o ? __ffs(o) - 1 : 0;
+        uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+        bool il = IL && (off & kInlineOffBit);
+        if (IL) off &= ~kInlineOffBit;
+        const bool ok = live && o && log_head - off < log_cap;
+        il = il && ok;
+        // where the entry's bytes live: the line's second half for the bucket's inline key, else the log
+        uint4 *home = reinterpret_cast<uint4 *>(il ? line + bkt * 128u + 64u : log + (off & log_mask));
+        uint4 ln = make_uint4(0u, 0u, 0u, 0u);
+        if (ok) ln = il ? ev : home[q];
+        const bool hit = ok && __shfl(u64_of(ln.z, ln.w), 0, 4) == key;
+        enum : uint32_t { kMissed = 0, kOlder = 1, kEqual = 2, kRaised = 3 };
+        uint32_t d = kMissed;
+        uint4 nl = ln;
+        if (q == 1 && hit) {   // ln: entry bytes 16..31; r: the record's
+            uint32_t w4 = ln.x, w5 = ln.y, ver = ln.z;
+            const uint32_t r_state = (r.x >> 16) & 0xFFu, r_cid = r.y >> 24, r_ver = r.z;
+            const uint64_t its = ((uint64_t)r_ver << 8) | r_cid, cur = ((uint64_t)ver << 8) | (w5 >> 24);
+            if (its > cur) {   // hermes_exec_inv, the newer INV
+                d = kRaised;
+                const uint32_t st = (w4 >> 16) & 0xFFu;
+                const uint32_t ns = st == kValid ? kInvalid : (st == kWrite || st == kReplay) ? kInvalidWrite : st;
+                w4 = (w4 & 0xFF0000FFu) | ((kvs_value & 0xFFu) << 8) | (ns << 16);        // val_len, state
+                w5 = (w5 & 0x00FFFF00u) | ((r_cid & 0x7Fu) << 1) | (r_cid << 24);         // RMW flag 0, last writer, ts cid
+                ver = r_ver;
+            } else if (its == cur) {
+                d = kEqual;
+                w5 = (w5 & ~0xFEu) | ((r_cid & 0x7Fu) << 1);                              // last writer
+            } else {
+                d = kOlder;
+            }
+            if (d >= kEqual && r_state == kValid) w4 = (w4 & 0xFF00FFFFu) | ((uint32_t)kValid << 16);   // hermes_exec_val
+            nl.x = w4;
+            nl.y = w5;
+            nl.z = ver;
+        }
+        d = __shfl(d, 1, 4);
+        if (d == kRaised) {   // the value: bytes 33..63 here (byte 32 is the entry's own), the rest below
+            if (q == 2) nl = make_uint4((ln.x & 0xFFu) | (r.x & ~0xFFu), r.y, r.z, r.w);
+            if (q == 3) nl = r;
+        }
+        if (hit && q > 0 && !(nl.x == ln.x && nl.y == ln.y && nl.z == ln.z && nl.w == ln.w)) home[q] = nl;
+        if (BIG && d == kRaised) {   // (320-B entries: four runs, their loads before their stores)
+            for (uint32_t k0 = 1; k0 < chunks; k0 += 4) {
+                uint4 t[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    t[k] = k0 + k < chunks ? records[i * E4 + 4 * (k0 + k) + q] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (k0 + k < chunks) home[4 * (k0 + k) + q] = t[k];
+            }
+        }
+        const bool mine = q == 1 && live;
+        cnt[0] += mine && d == kRaised;
+        cnt[1] += mine && d == kEqual;
+        cnt[2] += mine && d == kOlder;
+        cnt[3] += mine && d == kMissed;
+    }
+    block_add<4>(cnt, result);
+}
+
+int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                         uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *records, uint64_t record_cap,
+                         unsigned long long *result, int device, hipStream_t s)
+{
+    if (g.entry_size % 64 || (line && g.entry_size != 64) || bkt_lo > bkt_hi) return -1;
+    if (hipMemsetAsync(result, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    if (bkt_lo == bkt_hi) return 0;
+    const uint32_t chunks = g.entry_size / 64;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    // a persistent grid striding over the range, sized like the census's
+    const void *fn = line ? (const void *)k_table_extract<true, false>
+                   : chunks > 1 ? (const void *)k_table_extract<false, true> : (const void *)k_table_extract<false, false>;
+    int bpc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kCensusBlock, 0) != hipSuccess || bpc <= 0) bpc = 4;
+    if (bpc > 8) bpc = 8;
+    const uint64_t per_step = (uint64_t)kCensusBktsPerBlock * kExtractK;
+    const uint64_t tiles = (bkt_hi - bkt_lo + per_step - 1) / per_step, cap = (uint64_t)cus * bpc;
+    const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kCensusBlock);
+    uint4 *rec = reinterpret_cast<uint4 *>(records);
+    if (line)
+        hipLaunchKernelGGL((k_table_extract<true, false>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
+                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
+    else if (chunks > 1)
+        hipLaunchKernelGGL((k_table_extract<false, true>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
+                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
+    else
+        hipLaunchKernelGGL((k_table_extract<false, false>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
+                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,
+                         uint64_t n, unsigned long long *result, hipStream_t s)
+{
+    const uint32_t chunks = g.entry_size / 64;
+    const bool big = chunks > 1;
+    if (g.entry_size % 64 || (line && big) || g.rmw_enabled) return -1;
+    if (hipMemsetAsync(result, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    if (!n) return 0;
+    int device = 0, cus = 0;
+    if (hipGetDevice(&device) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
+        cus = 256;
+    // as many blocks as the CUs hold at once (8 per CU at the instances' 8 waves per SIMD), striding over the records
+    const uint64_t blocks = (n + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock, cap = (uint64_t)cus * 8;
+    const dim3 grid((unsigned)(blocks < cap ? blocks : cap)), block(kCensusBlock);
+    const uint4 *rec = reinterpret_cast<const uint4 *>(records);
+    if (line)
+        hipLaunchKernelGGL((k_table_install<true, false>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
+                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
+    else if (big)
+        hipLaunchKernelGGL((k_table_install<false, true>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
+                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
+    else
+        hipLaunchKernelGGL((k_table_install<false, false>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
+                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -899,6 +899,71 @@ int hkv_table_census(hkv_table *t, hkv_census *host_out)
     return 0;
 }
 
+// Replica repair (hermeskv.h "Replica repair"). Both calls follow the census's rules: they read (and the install
+// writes) the table where its truth lives -- the lines for an INLINE table's inline keys -- convert nothing, leave
+// `conversions` and `inline_launches` alone, and are ordered after the table's last stream, which they become.
+static_assert(sizeof(hkv_extract_result) == 16 && sizeof(hkv_install_result) == 32, "the kernels' word indices");
+uint32_t hkv_extract_result_bytes(void) { return (uint32_t)sizeof(hkv_extract_result); }
+uint32_t hkv_install_result_bytes(void) { return (uint32_t)sizeof(hkv_install_result); }
+
+// the refusals the two calls share, before anything is launched
+static int repair_enter(hkv_table *t, const void *d_records, const void *d_result, const char *what)
+{
+    if (!t || !d_result) return fail(-1, "%s: null argument", what);
+    if (t->cfg.rmw_enabled) return fail(-2, "%s: the table has RMWs enabled (a record carries no RMW flag)", what);
+    if (((uintptr_t)d_records | (uintptr_t)d_result) & 15)
+        return fail(-1, "%s: d_records and d_result must be 16-byte aligned", what);
+    return 0;
+}
+
+static int repair_order(hkv_table *t, hipStream_t s)
+{
+    HIP_TRY(hipSetDevice(t->cfg.device));
+    if (t->last_stream != s) HIP_TRY(hipStreamSynchronize(t->last_stream));
+    if (t->stream != s) HIP_TRY(hipStreamSynchronize(t->stream));   // the host-pointer path's launches
+    return 0;
+}
+
+int hkv_table_extract_async(hkv_table *t, uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, void *d_records,
+                            uint64_t record_cap, hkv_extract_result *d_result, void *stream)
+{
+    if (int rc = repair_enter(t, d_records, d_result, "extract")) return rc;
+    if (bkt_hi > t->cfg.num_bkts || bkt_lo > bkt_hi)
+        return fail(-1, "extract: bucket range [%llu, %llu) of %llu buckets", (unsigned long long)bkt_lo,
+                    (unsigned long long)bkt_hi, (unsigned long long)t->cfg.num_bkts);
+    if (record_cap && !d_records) return fail(-1, "extract: record_cap without d_records");
+    srv_stop(t);   // the serving kernel of the host-pointer path writes the table outside every stream order
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);   // against hkv_table_populate (geo.log_head)
+    if (int rc = repair_order(t, s)) return rc;
+    const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
+    if (int rc = launch_table_extract(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr, bkt_lo, bkt_hi, min_ts,
+                                      static_cast<uint8_t *>(d_records), record_cap,
+                                      reinterpret_cast<unsigned long long *>(d_result), t->cfg.device, s))
+        return fail(-3, "extract launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    t->last_stream = s;
+    TRACE("extract (%s) [%llu, %llu)", inl ? "INLINE" : "LOG", (unsigned long long)bkt_lo, (unsigned long long)bkt_hi);
+    return 0;
+}
+
+int hkv_table_install_async(hkv_table *t, const void *d_records, uint64_t n, hkv_install_result *d_result, void *stream)
+{
+    if (int rc = repair_enter(t, d_records, d_result, "install")) return rc;
+    if (n && !d_records) return fail(-1, "install: records without d_records");
+    srv_stop(t);
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (int rc = repair_order(t, s)) return rc;
+    const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
+    if (int rc = launch_table_install(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr,
+                                      static_cast<const uint8_t *>(d_records), n,
+                                      reinterpret_cast<unsigned long long *>(d_result), s))
+        return fail(-3, "install launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    t->last_stream = s;
+    TRACE("install (%s) %llu records", inl ? "INLINE" : "LOG", (unsigned long long)n);
+    return 0;
+}
+
 int hkv_hash_ids(const uint32_t *d_ids, uint64_t *d_keys_second, int64_t n, void *stream)
 {
     if (launch_hash_ids(d_ids, d_keys_second, n, (hipStream_t)stream)) return fail(-5, "hash launch failed");

@@ -134,6 +134,61 @@ class Census:
         return self.offender_keys[:n].cpu().numpy().view(np.uint64)
 
 
+@dataclasses.dataclass
+class Extract:
+    """The result of HermesKV.extract(), still on the device. `tensor`: the record buffer (uint8, cap x E: each
+    record an entry image under the digest's mask, include/hermeskv.h "Replica repair"), `result`:
+    hkv_extract_result as two int64 words. Nothing is read back until a count is asked for: records (how many
+    qualified, possibly more than the buffer holds), scanned_keys and written = min(records, cap) synchronise."""
+    tensor: torch.Tensor
+    result: torch.Tensor
+    entry: int
+
+    @property
+    def cap(self) -> int:
+        return self.tensor.numel() // self.entry
+
+    def host(self) -> dict:
+        r, s = (int(x) & 0xFFFFFFFFFFFFFFFF for x in self.result.cpu().tolist())
+        return {"records": r, "scanned_keys": s}
+
+    @property
+    def records(self) -> int:
+        return self.host()["records"]
+
+    @property
+    def scanned_keys(self) -> int:
+        return self.host()["scanned_keys"]
+
+    @property
+    def written(self) -> int:
+        return min(self.records, self.cap)
+
+    def records_host(self) -> np.ndarray:
+        """the written records as [written][E] uint8, in no particular order"""
+        n = self.written
+        return self.tensor[:n * self.entry].cpu().numpy().reshape(n, self.entry)
+
+
+INSTALL_FIELDS = ("raised", "equal", "older", "missed")
+
+
+@dataclasses.dataclass
+class InstallResult:
+    """The result of HermesKV.install(), still on the device: hkv_install_result as four int64 words (raised,
+    equal, older, missed, counted against the table as it was before the install). host() and the attributes
+    of those names synchronise; `tensor` adds up across installs without a host read."""
+    tensor: torch.Tensor
+
+    def host(self) -> dict:
+        return {k: int(x) & 0xFFFFFFFFFFFFFFFF for k, x in zip(INSTALL_FIELDS, self.tensor.cpu().tolist())}
+
+    def __getattr__(self, name: str):
+        if name in INSTALL_FIELDS:
+            return self.host()[name]
+        raise AttributeError(name)
+
+
 class HermesKV:
     """One HermesKV replica: a MICA-herd table in HBM plus the batch path on it."""
 
@@ -441,6 +496,62 @@ class HermesKV:
         v = HkvCensus()
         check(_L.hkv_table_census(self.h, ctypes.byref(v)), "hkv_table_census")
         return _census_dict(bytes(v))
+
+    # -- replica repair (include/hermeskv.h, "Replica repair")
+    def extract(self, bkt_range: tuple[int, int] | None = None, min_ts: int = 0, out: torch.Tensor | None = None,
+                cap: int | None = None, stream: torch.cuda.Stream | None = None,
+                result: torch.Tensor | None = None) -> "Extract":
+        """hkv_table_extract_async: one record per live key of the buckets bkt_range = (lo, hi) (default: all) whose
+        packed timestamp (version << 8 | cid) is at least min_ts, read from whichever residency the table is in
+        (nothing is converted), asynchronously on `stream` (default: torch's current). out: a uint8 device buffer
+        to write into (its whole records are the capacity) instead of a new one of `cap` records (default: the
+        table's num_keys); result: two int64 words to write the counts into. Records past the capacity are counted,
+        not written. min_ts only saves volume: the protocol has no global watermark, so whether the keys it leaves
+        out are current at the target is the caller's to know. Not for tables with RMWs."""
+        dev = torch.device("cuda", self.device)
+        E = self.sizes.entry
+        if out is None:
+            out = torch.empty(max(int(self.num_keys if cap is None else cap), 1) * E, dtype=torch.uint8, device=dev)
+            n_cap = int(self.num_keys if cap is None else cap)
+        else:
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+            n_cap = out.numel() // E if cap is None else int(cap)
+            assert n_cap * E <= out.numel()
+        if result is None:
+            result = torch.empty(2, dtype=torch.int64, device=dev)
+        assert result.is_cuda and result.dtype == torch.int64 and result.is_contiguous() and result.numel() >= 2
+        lo, hi = (0, self.cfg.num_bkts) if bkt_range is None else (int(bkt_range[0]), int(bkt_range[1]))
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_extract_async(self.h, lo, hi, int(min_ts), ctypes.c_void_p(out.data_ptr()), n_cap,
+                                         ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)),
+              "hkv_table_extract_async")
+        return Extract(out[:n_cap * E], result[:2], E)
+
+    def install(self, records, n: int | None = None, stream: torch.cuda.Stream | None = None,
+                result: torch.Tensor | None = None) -> "InstallResult":
+        """hkv_table_install_async: apply n records (an Extract, or a uint8 device tensor of whole records), no key
+        twice among them, as the reference would apply one INV per record (sender = the record's ts cid) and then
+        one VAL per record whose source state was VALID: newer records install value, timestamp and state, equal
+        ones touch what an INV and a VAL of that timestamp touch, older ones nothing, unknown keys are misses.
+        n omitted: for an Extract min(records, capacity), which is read on the host (a synchronisation: pass n to
+        stay on the stream); for a tensor, all its whole records. Asynchronous on `stream`. A repair is sound
+        while this table takes no client operations; INVs it receives meanwhile are safe, the install being
+        timestamp-guarded. Re-admission to the membership is not part of it. Not for tables with RMWs."""
+        E = self.sizes.entry
+        t = records.tensor if isinstance(records, Extract) else records
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+        if n is None:
+            n = records.written if isinstance(records, Extract) else t.numel() // E
+        n = int(n)
+        assert 0 <= n and n * E <= t.numel()
+        if result is None:
+            result = torch.empty(4, dtype=torch.int64, device=t.device)
+        assert result.is_cuda and result.dtype == torch.int64 and result.is_contiguous() and result.numel() >= 4
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        self.launches += 1
+        check(_L.hkv_table_install_async(self.h, ctypes.c_void_p(t.data_ptr()), n, ctypes.c_void_p(result.data_ptr()),
+                                         ctypes.c_void_p(s)), "hkv_table_install_async")
+        return InstallResult(result[:4])
 
     def device_index(self) -> int:
         return _L.hkv_device_index(self.h)

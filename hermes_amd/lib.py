@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 HERE = os.path.dirname(os.path.abspath(__file__))
 # HKV_LIB: another build of the same library (A/B timing of two revisions in one GPU session)
 LIB_PATH = os.environ.get("HKV_LIB") or os.path.join(HERE, "libhermeskv.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(f"{LIB_PATH} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)")
@@ -58,6 +58,17 @@ class HkvCensus(ctypes.Structure):
                 ("offenders", ctypes.c_uint64)]
 
 
+class HkvExtractResult(ctypes.Structure):
+    """hkv_extract_result (include/hermeskv.h, "Replica repair")"""
+    _fields_ = [("records", ctypes.c_uint64), ("scanned_keys", ctypes.c_uint64)]
+
+
+class HkvInstallResult(ctypes.Structure):
+    """hkv_install_result: counted against the table as it was before the install"""
+    _fields_ = [("raised", ctypes.c_uint64), ("equal", ctypes.c_uint64), ("older", ctypes.c_uint64),
+                ("missed", ctypes.c_uint64)]
+
+
 class Membership(ctypes.Structure):
     """spacetime_group_membership (8 bytes) by value. Declared as one 64-bit field: the SysV
     x86-64 ABI classifies both as a single INTEGER eightbyte, and libffi handles a scalar
@@ -94,6 +105,10 @@ _L.hkv_copy_lines.argtypes = [_P, _P, ctypes.c_uint64, ctypes.c_uint64]
 _L.hkv_census_bytes.restype = ctypes.c_uint32
 _L.hkv_table_census_async.argtypes = [_P, _P, _P, ctypes.c_uint64, _P]
 _L.hkv_table_census.argtypes = [_P, ctypes.POINTER(HkvCensus)]
+_L.hkv_extract_result_bytes.restype = ctypes.c_uint32
+_L.hkv_install_result_bytes.restype = ctypes.c_uint32
+_L.hkv_table_extract_async.argtypes = [_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]
+_L.hkv_table_install_async.argtypes = [_P, _P, ctypes.c_uint64, _P, _P]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

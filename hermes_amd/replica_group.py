@@ -730,6 +730,83 @@ def group_census(kvs: HermesKV, group=None, live_ranks=None) -> dict:
             "not_valid": [r[3] for r in rows]}
 
 
+def _bucket_chunks(num_bkts: int, chunk_buckets: int | None):
+    step = int(chunk_buckets) if chunk_buckets else int(num_bkts)
+    assert step > 0
+    return [(lo, min(lo + step, int(num_bkts))) for lo in range(0, int(num_bkts), step)]
+
+
+def resync(dst: HermesKV, src: HermesKV, chunk_buckets: int | None = None, min_ts: int = 0) -> dict:
+    """Repair a stale replica from a live one, both tables in this process (loopback groups, one-GPU tests): walk
+    `src` in chunks of chunk_buckets buckets (default: the whole table at once), HermesKV.extract each chunk into
+    one reused buffer and HermesKV.install it into `dst`, which may have another bucket count, log order or
+    residency. Returns the summed install counts {raised, equal, older, missed} plus records and scanned_keys.
+    Each chunk's record count is read on the host (the buffer is sized once, for the fullest chunk possible:
+    eight keys per bucket, at most the source's keys). After a resync of a quiet group the two tables' census
+    digests are equal. Sound only while `dst` takes no client operations; INVs it receives meanwhile are safe,
+    the install being timestamp-guarded (an older record changes nothing). min_ts only saves volume -- there is
+    no global watermark in a per-key protocol. Membership re-admission is not done here."""
+    assert dst.sizes == src.sizes, "records of one entry size only"
+    chunks = _bucket_chunks(src.cfg.num_bkts, chunk_buckets)
+    cap = max(1, min(int(src.num_keys), 8 * max(hi - lo for lo, hi in chunks)))
+    dev = torch.device("cuda", src.device)
+    buf = torch.empty(cap * src.sizes.entry, dtype=torch.uint8, device=dev)
+    res = torch.empty(2, dtype=torch.int64, device=dev)
+    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    records = scanned = 0
+    for lo, hi in chunks:
+        x = src.extract((lo, hi), min_ts, out=buf, result=res)
+        h = x.host()
+        assert h["records"] <= cap, "more live keys in a chunk than slots"
+        records, scanned = records + h["records"], scanned + h["scanned_keys"]
+        if h["records"]:
+            tot += dst.install(x, n=h["records"]).tensor
+    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+    out.update(records=records, scanned_keys=scanned)
+    return out
+
+
+def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buckets: int | None, min_ts: int = 0) -> dict:
+    """resync() across ranks. Collective: every rank of `group` calls it with the same arguments and its own table
+    (tables of one entry size; bucket counts may differ -- the chunks walk the source's, whose count is broadcast
+    first). Per chunk the source rank extracts and broadcasts the record count, then the records (CUDA tensors
+    through torch.distributed: gloo and NCCL / RCCL alike); only the ranks in stale_ranks install, the others
+    just take part in the broadcasts. Returns this rank's summed install counts (zeros where it did not install)
+    plus records and scanned_keys of the source. The same conditions as resync(): a stale rank takes no client
+    operations meanwhile, and nobody is re-admitted to the membership here."""
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
+    stale = {int(r) for r in stale_ranks}
+    assert source_rank not in stale
+    dev = torch.device("cuda", kvs.device)
+    E = kvs.sizes.entry
+    geo = torch.tensor([kvs.cfg.num_bkts, kvs.num_keys], dtype=torch.int64, device=dev)
+    dist.broadcast(geo, src, group=group)
+    num_bkts, src_keys = (int(v) for v in geo.cpu().tolist())
+    chunks = _bucket_chunks(num_bkts, chunk_buckets)
+    cap = max(1, min(src_keys, 8 * max(hi - lo for lo, hi in chunks)))
+    buf = torch.empty(cap * E, dtype=torch.uint8, device=dev)
+    res = torch.zeros(2, dtype=torch.int64, device=dev)
+    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    records = scanned = 0
+    for lo, hi in chunks:
+        if rank == source_rank:
+            kvs.extract((lo, hi), min_ts, out=buf, result=res)
+        dist.broadcast(res, src, group=group)
+        n, sc = (int(v) for v in res.cpu().tolist())
+        assert n <= cap, "more live keys in a chunk than slots"
+        records, scanned = records + n, scanned + sc
+        if not n:
+            continue
+        dist.broadcast(buf[:n * E], src, group=group)
+        if rank in stale:
+            tot += kvs.install(buf, n=n).tensor
+    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+    out.update(records=records, scanned_keys=scanned)
+    return out
+
+
 class LoopbackGroup:
     """N replicas driven phase by phase in one process; the collectives are tensor copies with
     exactly the layouts the RCCL driver produces (all-gather: row p = rank p's slab;

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define HKV_ABI_VERSION 9
+#define HKV_ABI_VERSION 10
 
 /* ------------------------------------------------------------------ reference types
  * Declared here only when the reference's own spacetime.h has not been included; the
@@ -335,6 +335,71 @@ int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender
                            uint64_t offender_cap, void *stream);
 /* the same, synchronous, into host memory, no offender list */
 int hkv_table_census(hkv_table *t, hkv_census *host_out);
+
+/* Replica repair (ABI 10): a table's replicated state as records, and their timestamp-guarded install into
+ * another table, of either residency and of any geometry (bucket count, log capacity, log order). Where
+ * hkv_copy_index / hkv_copy_log ship a byte image -- identical geometry, LOG only, overwriting whatever the
+ * target has learnt since -- a record is keyed by key and applied by the protocol's own rules.
+ *
+ * Record. An entry image of E bytes (64, or 320 with big objects) that keeps exactly the bytes the digest keeps
+ * -- key 8..15, state 18, ts cid 23, ts version 24..27, value 33..33+ST_VALUE_SIZE-1 -- and is zero in every
+ * other byte. The digest's h of a record is therefore that of the entry it came from, and the sum of h over an
+ * unfiltered extract of a whole table is its census's digest_sum.
+ *
+ * Extract. One record per live slot (the census's definition: in use, and log_head - offset < log_cap) of the
+ * buckets [bkt_lo, bkt_hi) whose packed timestamp (version << 8 | cid) is at least min_ts, written compacted to
+ * d_records in no particular order. hkv_extract_result.records is the number that qualify and may exceed
+ * record_cap: records past record_cap are not written and nothing at or past min(records, record_cap) * E
+ * bytes of d_records is touched. d_result is overwritten, not accumulated. The residency rule is the
+ * census's: the table is read as it is (an INLINE table's inline keys from their lines, never from their stale
+ * log copies), nothing is converted, and the layout counters (conversions, inline_launches) do not move. The
+ * bucket range lets a caller stream a large table through a bounded buffer; one extract holds no key twice.
+ * min_ts only reduces the volume. Whether leaving out the older keys is sound is the caller's business: the
+ * protocol orders writes per key, so there is no global watermark below which a target is known to be current.
+ *
+ * Install. The result is defined by the reference: installing the n records R into a table equals the
+ * reference applying two batches, one after the other, under the table's membership (no field of which these
+ * two batch types read):
+ *   an `invs` batch of one INV per record -- opcode ST_OP_INV, the record's key, timestamp and value, sender =
+ *   the record's ts cid, val_len ST_VALUE_SIZE (as the worker's INVs carry it), RMW flag 0;
+ *   then a `vals` batch of one VAL (key, timestamp) for every record whose state byte is VALID.
+ * So a record newer than the key's timestamp installs value and timestamp and moves the state as
+ * hermes_exec_inv does (VALID at the end when the source was VALID); a record of equal timestamp touches only
+ * what an INV and a VAL of that timestamp touch; an older record changes nothing; a key the source caught
+ * mid-write (state not VALID) is left not VALID at that timestamp -- the message a shadow replica would have
+ * received; a key the target does not hold is a miss (there are no inserts after populate). The lock byte,
+ * ack_bv, op buffer index and last-local-write timestamp are left as those two batches leave them, and the
+ * per-line F/X/Y/T words of the batch engines are not touched. On an INLINE table the inline keys are read and
+ * written in their lines only; nothing is converted and the layout counters do not move.
+ * The caller guarantees that no key occurs twice among the n records (as for HKV_BATCH_UNIQUE: each record is
+ * then its key's only one and is applied in a single pass, in any order); the records of one extract have this
+ * property. A duplicate breaks the result.
+ * hkv_install_result counts, against the table as it was before the call: raised (record ts > key ts), equal,
+ * older and missed; d_result is overwritten.
+ *
+ * Both calls are asynchronous on `stream`, ordered after the launches already enqueued on the table's last
+ * stream, one caller at a time per table, and stop a live serving kernel of the host-pointer path first (as
+ * hkv_table_census_async). Both refuse, with a negative code and a message in hkv_last_error() before
+ * anything is launched: a table with rmw_enabled (a record carries no RMW flag, and an RMW build's INVs
+ * depend on it); d_records or d_result not 16-byte aligned; bkt_hi > num_bkts or bkt_lo > bkt_hi.
+ * Out of scope: re-admitting the repaired replica to the membership. A repair is sound while the target takes
+ * no client operations; INVs it receives meanwhile are safe, the install being timestamp-guarded. */
+typedef struct hkv_extract_result {
+    uint64_t records;            /* records that qualify (may exceed record_cap) */
+    uint64_t scanned_keys;       /* live slots of the bucket range, whatever their timestamp */
+} hkv_extract_result;
+typedef struct hkv_install_result {
+    uint64_t raised;             /* record ts > key ts: value, timestamp and state installed */
+    uint64_t equal;              /* record ts == key ts */
+    uint64_t older;              /* record ts < key ts: nothing changed */
+    uint64_t missed;             /* the table does not hold the key */
+} hkv_install_result;
+uint32_t hkv_extract_result_bytes(void);   /* sizeof, for bindings */
+uint32_t hkv_install_result_bytes(void);
+int hkv_table_extract_async(hkv_table *t, uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, void *d_records,
+                            uint64_t record_cap, hkv_extract_result *d_result, void *stream);
+int hkv_table_install_async(hkv_table *t, const void *d_records, uint64_t n, hkv_install_result *d_result,
+                            void *stream);
 
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
