@@ -188,16 +188,12 @@ __device__ __forceinline__ void note_state(const BatchArgs &a, int64_t i, const 
 // words, phys_of, fw_index -- stays its log offset; only the bytes' home differs, and that is a function of the
 // bucket, so of the key, which every element, entry image and shadow holds.
 constexpr uint32_t kEntInline = 0x80000000u;
-__device__ __forceinline__ uint8_t *line_entry(const BatchArgs &a, uint64_t key)
-{
-    return a.line + ((key & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 128u + 64u;
-}
 template <bool IL>
 __device__ __forceinline__ uint32_t ent_id(uint32_t e) { return IL ? e & ~kEntInline : e; }
 template <bool IL>
 __device__ __forceinline__ uint8_t *entry_home(const BatchArgs &a, uint32_t e, uint64_t key)
 {
-    if (IL && (e & kEntInline)) return line_entry(a, key);
+    if (IL && (e & kEntInline)) return line_entry(a.line, a.g, key);
     return entry_of(a, ent_id<IL>(e));
 }
 // Live entries never overlap and are at least 64 B long, so their first 64-B lines are distinct.
@@ -434,20 +430,20 @@ __device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         if (IL) {
-            const uint4 *l = reinterpret_cast<const uint4 *>(a.line + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 128u);
+            const uint4 *l = line_words(a.line, bucket_of(a.g, key[k]));
             v[k] = probe[k] ? l[q] : make_uint4(0u, 0u, 0u, 0u);
             ev[k] = probe[k] ? l[4 + q] : make_uint4(0u, 0u, 0u, 0u);
         } else {
-            v[k] = probe[k] ? reinterpret_cast<const uint4 *>(a.index + ((key[k] & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u)[q]
-                            : make_uint4(0u, 0u, 0u, 0u);
+            v[k] = probe[k] ? bucket_words(a.index, bucket_of(a.g, key[k]))[q] : make_uint4(0u, 0u, 0u, 0u);
         }
     }
     bool il[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-        const uint64_t s0 = (uint64_t)v[k].x | ((uint64_t)v[k].y << 32);
-        const uint64_t s1 = (uint64_t)v[k].z | ((uint64_t)v[k].w << 32);
-        const uint32_t tag = (uint32_t)(key[k] >> 48);
+        // group_probe (hkv_table_dev.h) with its tag test and slot mask written out: through slot_matches or
+        // group_slots k_local_pre and k_unique_rows change their register counts (profiles/table_dev_registers.txt)
+        const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
+        const uint32_t tag = key_tag(key[k]);
         const bool mt0 = probe[k] && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
         const bool mt1 = probe[k] && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
         const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu;
@@ -456,22 +452,17 @@ __device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *
 #pragma unroll
         for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
         const int first = o ? __ffs(o) - 1 : 0;
-        uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
-        il[k] = false;
-        if (IL) {
-            il[k] = (off & kInlineOffBit) != 0;
-            off &= ~kInlineOffBit;
-        }
-        ok[k] = probe[k] && o && a.g.log_head - off < a.g.log_cap;
+        const uint64_t raw = group_slot_word(slot_off_raw(s0), slot_off_raw(s1), first), off = off_of<IL>(raw);
+        ok[k] = probe[k] && o && in_log_window(a.g, off);
         phys[k] = off & a.g.log_mask;
-        if (IL) il[k] = il[k] && ok[k];
+        il[k] = off_is_inline<IL>(raw) && ok[k];
     }
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         if (IL) {
             ln[k] = ev[k];
             if (!il[k]) ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
-            if (home) home[k] = il[k] ? line_entry(a, key[k]) : a.log + phys[k];
+            if (home) home[k] = il[k] ? line_entry(a.line, a.g, key[k]) : a.log + phys[k];
             if (inl) inl[k] = il[k];
         } else {
             ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
@@ -2953,24 +2944,22 @@ __device__ void hp_partition(const HostPartCommon &p, HpLds &L, int g, int nb, u
     uint64_t phys = 0;
     if (live && !skip_elem_os(type, x[8], x[9])) {
         const uint64_t key = *reinterpret_cast<const uint64_t *>(x);
-        const uint4 *bk = reinterpret_cast<const uint4 *>(p.index + ((key & 0xFFFFFFFFFFFFULL) & p.g.bkt_mask) * 64u);
+        const uint4 *bk = bucket_words(p.index, bucket_of(p.g, key));
         const uint4 q0 = bk[0], q1 = bk[1], q2 = bk[2], q3 = bk[3];
-        const uint64_t sl[8] = {(uint64_t)q0.x | ((uint64_t)q0.y << 32), (uint64_t)q0.z | ((uint64_t)q0.w << 32),
-                                (uint64_t)q1.x | ((uint64_t)q1.y << 32), (uint64_t)q1.z | ((uint64_t)q1.w << 32),
-                                (uint64_t)q2.x | ((uint64_t)q2.y << 32), (uint64_t)q2.z | ((uint64_t)q2.w << 32),
-                                (uint64_t)q3.x | ((uint64_t)q3.y << 32), (uint64_t)q3.z | ((uint64_t)q3.w << 32)};
-        const uint32_t tag = (uint32_t)(key >> 48);
+        const uint64_t sl[8] = {u64_of(q0.x, q0.y), u64_of(q0.z, q0.w), u64_of(q1.x, q1.y), u64_of(q1.z, q1.w),
+                                u64_of(q2.x, q2.y), u64_of(q2.z, q2.w), u64_of(q3.x, q3.y), u64_of(q3.z, q3.w)};
+        const uint32_t tag = key_tag(key);
         int hit = -1;
 #pragma unroll
         for (int q = 7; q >= 0; --q)
-            if ((sl[q] & 1u) && ((uint32_t)(sl[q] >> 1) & 0x7FFFFFu) == tag) hit = q;
+            if (slot_matches(sl[q], tag)) hit = q;
         if (hit >= 0) {
-            const uint64_t off = sl[hit] >> 24;
-            if (p.g.log_head - off < p.g.log_cap) {
+            const uint64_t off = slot_off_raw(sl[hit]);
+            if (in_log_window(p.g, off)) {
                 phys = off & p.g.log_mask;
                 const uint4 *ln = reinterpret_cast<const uint4 *>(p.log + phys);
                 const uint4 l0 = ln[0], l1 = ln[1], l2 = ln[2], l3 = ln[3];
-                if (((uint64_t)l0.z | ((uint64_t)l0.w << 32)) == key) {
+                if (u64_of(l0.z, l0.w) == key) {
                     e = (uint32_t)(phys / p.g.entry_unit);
                     L.sln[s * 4 + 0] = l0;
                     L.sln[s * 4 + 1] = l1;

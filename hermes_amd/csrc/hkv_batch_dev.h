@@ -11,6 +11,7 @@
 
 #include "hkv_exec.h"
 #include "hkv_internal.h"
+#include "hkv_table_dev.h"
 
 namespace hkv {
 

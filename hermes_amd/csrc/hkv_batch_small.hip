@@ -146,20 +146,18 @@ __global__ __launch_bounds__(kSmallThreads) void k_small(BatchArgs a)
                 if (v.type == kInvs) atomicMax(&ns[v.b], v.pos);   // hermes_skip_inv: the last one wins
             } else {
                 const uint64_t key = h.a;
-                const uint4 *bk = reinterpret_cast<const uint4 *>(a.index + ((key & 0xFFFFFFFFFFFFULL) & a.g.bkt_mask) * 64u);
+                const uint4 *bk = bucket_words(a.index, bucket_of(a.g, key));
                 const uint4 q0 = bk[0], q1 = bk[1], q2 = bk[2], q3 = bk[3];
-                const uint64_t sl[8] = {(uint64_t)q0.x | ((uint64_t)q0.y << 32), (uint64_t)q0.z | ((uint64_t)q0.w << 32),
-                                        (uint64_t)q1.x | ((uint64_t)q1.y << 32), (uint64_t)q1.z | ((uint64_t)q1.w << 32),
-                                        (uint64_t)q2.x | ((uint64_t)q2.y << 32), (uint64_t)q2.z | ((uint64_t)q2.w << 32),
-                                        (uint64_t)q3.x | ((uint64_t)q3.y << 32), (uint64_t)q3.z | ((uint64_t)q3.w << 32)};
-                const uint32_t tag = (uint32_t)(key >> 48);
+                const uint64_t sl[8] = {u64_of(q0.x, q0.y), u64_of(q0.z, q0.w), u64_of(q1.x, q1.y), u64_of(q1.z, q1.w),
+                                        u64_of(q2.x, q2.y), u64_of(q2.z, q2.w), u64_of(q3.x, q3.y), u64_of(q3.z, q3.w)};
+                const uint32_t tag = key_tag(key);
                 int hit = -1;
 #pragma unroll
                 for (int q = 7; q >= 0; --q)
-                    if ((sl[q] & 1u) && ((uint32_t)(sl[q] >> 1) & 0x7FFFFFu) == tag) hit = q;
+                    if (slot_matches(sl[q], tag)) hit = q;
                 if (hit >= 0) {
-                    const uint64_t off = sl[hit] >> 24;
-                    if (a.g.log_head - off < a.g.log_cap) {
+                    const uint64_t off = slot_off_raw(sl[hit]);
+                    if (in_log_window(a.g, off)) {
                         const uint64_t phys = off & a.g.log_mask;
                         const U64x2 *ln = reinterpret_cast<const U64x2 *>(a.log + phys);
                         const U64x2 l0 = ln[0], l1 = ln[1], l2 = ln[2];  // key at 8, meta at 16..32

@@ -12,6 +12,7 @@
 
 #include "hkv_exec.h"
 #include "hkv_internal.h"
+#include "hkv_table_dev.h"
 
 namespace hkv {
 
@@ -103,7 +104,7 @@ __global__ void k_pop_buckets(const uint32_t *__restrict__ sk, const uint32_t *_
         int use = -1;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if ((((uint32_t)(s[j] >> 1)) & 0x7FFFFFu) == tag || (s[j] & 1u) == 0) use = j;
+            if (slot_tag(s[j]) == tag || !slot_in_use(s[j])) use = j;
         if (use < 0) {
             use = (int)(tag & 7u);
             ++ev;
@@ -223,17 +224,13 @@ __global__ __launch_bounds__(256) void k_layout_convert(const uint8_t *index, ui
     const uint64_t b = (uint64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
     const bool live = b < num_bkts;   // (the four lanes of a group share b: a group is live or idle as a whole)
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
-    if (live) v = reinterpret_cast<const uint4 *>(index + b * 64u)[q];
-    const uint64_t s0 = (uint64_t)v.x | ((uint64_t)v.y << 32), s1 = (uint64_t)v.z | ((uint64_t)v.w << 32);
-    const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
-    const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
-    uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
-#pragma unroll
-    for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+    if (live) v = bucket_words(index, b)[q];
+    const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
+    const uint32_t o = group_slots(live && slot_in_use(s0), live && slot_in_use(s1), gbase);   // the slots in use
     const int first = o ? __ffs(o) - 1 : 0;
-    const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
+    const uint64_t off = group_slot_word(slot_off_raw(s0), slot_off_raw(s1), first);
     if (!live) return;
-    uint4 *ln = reinterpret_cast<uint4 *>(line + b * 128u);
+    uint4 *ln = line_words(line, b);
     uint4 *ent = reinterpret_cast<uint4 *>(log + (off & log_mask));
     if (TO_INLINE) {
         if (o && (first >> 1) == q) {
@@ -284,7 +281,58 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)   // the splitmix64 finali
     x ^= x >> 31;
     return x;
 }
-__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+
+// N per-thread values -> out[0..N): per wave by shuffles, per block through LDS, then one atomic per non-zero field
+// and block (0 is neutral). Field KMAX combines by max, KXOR by xor (-1: none), the rest by add. Every thread calls it.
+template <int KMAX = -1, int KXOR = -1, class T, int N>
+__device__ __forceinline__ void block_reduce(const T (&v)[N], unsigned long long *out)
+{
+    using U = unsigned long long;
+    const auto red_op = [](int k, U x, U y) { return k == KMAX ? (y > x ? y : x) : k == KXOR ? x ^ y : x + y; };
+    __shared__ unsigned long long sh[kCensusBlock / 64][N];
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        unsigned long long x = v[k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) x = red_op(k, x, __shfl_xor(x, d));
+        if (lane == 0) sh[threadIdx.x >> 6][k] = x;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const int k = threadIdx.x;
+        unsigned long long x = sh[0][k];
+        for (int w = 1; w < kCensusBlock / 64; ++w) x = red_op(k, x, sh[w][k]);
+        if (x) {
+            if (k == KMAX) atomicMax(&out[k], x);
+            else if (k == KXOR) atomicXor(&out[k], x);
+            else atomicAdd(&out[k], x);
+        }
+    }
+}
+
+// The passes' persistent grid: as many blocks per CU as the kernel's registers let a CU hold at once (at most cap;
+// fn NULL: cap itself), so the blocks all start and end together -- a grid that needs a second, partial round of
+// blocks ends with idle CUs. No block waits for another, so any grid gives the same result.
+dim3 persistent_grid(const void *fn, uint64_t items, uint64_t items_per_step, int device, int cap)
+{
+    int cus = 0, bpc = cap;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
+    if (fn && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kCensusBlock, 0) != hipSuccess || bpc <= 0)) bpc = 4;
+    if (bpc > cap) bpc = cap;
+    const uint64_t steps = (items + items_per_step - 1) / items_per_step, most = (uint64_t)cus * bpc;
+    return dim3((unsigned)(steps < most ? steps : most));
+}
+
+// f(IL, BIG) as two std::bool_constants for a pass's instance: the inline residency's lines (never with big
+// entries), or index and log with entries of 64 B or more
+template <class F>
+void with_instance(bool il, bool big, F &&f)
+{
+    if (il) f(std::true_type{}, std::false_type{});
+    else if (big) f(std::false_type{}, std::true_type{});
+    else f(std::false_type{}, std::false_type{});
+}
 }  // namespace
 
 template <bool IL, bool BIG>
@@ -300,32 +348,24 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_census(const uint8_t *__
     uint32_t n_keys = 0, n_dead = 0, n_obi = 0, n_lines = 0, n_off = 0, n_state[6] = {0, 0, 0, 0, 0, 0},
              n_cid[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t max_ts = 0, dsum = 0, dxor = 0;
-    // the masks of this lane's two words of an entry's first 64 B (words 2q and 2q + 1): key; state and ts cid,
-    // ts version; the value from byte 33 on
-    const uint64_t mask_a = q == 0 ? 0ull : q == 1 ? 0xFF00000000FF0000ull : q == 2 ? 0xFFFFFFFFFFFFFF00ull : ~0ull;
-    const uint64_t mask_b = q == 1 ? 0x00000000FFFFFFFFull : ~0ull;
+    const uint64_t mask_a = digest_mask_a(q), mask_b = digest_mask_b(q);
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
         const uint64_t b = tile * kCensusBktsPerBlock + (threadIdx.x >> 2);
         const bool live = b < num_bkts;   // (the four lanes of a group share b)
         uint4 v = make_uint4(0u, 0u, 0u, 0u), iv = v;
         if (live) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(IL ? line + b * 128u : index + b * 64u);
+            const uint4 *src = IL ? line_words(line, b) : bucket_words(index, b);
             v = src[q];
             if (IL) iv = src[4 + q];
         }
         const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
-        const uint32_t g0 = (uint32_t)(__ballot(live && (s0 & 1u)) >> gbase) & 0xFu;
-        const uint32_t g1 = (uint32_t)(__ballot(live && (s1 & 1u)) >> gbase) & 0xFu;
-        uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is in use
-#pragma unroll
-        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+        uint32_t o = group_slots(live && slot_in_use(s0), live && slot_in_use(s1), gbase);   // the slots in use
         while (o) {   // (group-uniform: the four lanes of a group stay together)
             const int j = __ffs(o) - 1;
             o &= o - 1;
-            uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
-            const bool il = IL && (off & kInlineOffBit);
-            if (IL) off &= ~kInlineOffBit;
-            if (log_head - off >= log_cap) {   // the lookup's window check: the log has overwritten the entry
+            const uint64_t raw = slot_off_raw(group_slot_word(s0, s1, j)), off = off_of<IL>(raw);
+            const bool il = off_is_inline<IL>(raw);
+            if (!in_log_window(log_head, log_cap, off)) {   // the log has overwritten the entry
                 ++n_dead;
                 continue;
             }
@@ -395,31 +435,7 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_census(const uint8_t *__
         r[kCsLines] = n_lines;
         r[kCsOffenders] = n_off;
     }
-    __shared__ unsigned long long sh[kCensusBlock / 64][kCensusWords];
-#pragma unroll
-    for (int k = 0; k < kCensusWords; ++k) {
-        unsigned long long x = r[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const unsigned long long y = __shfl_xor(x, d);
-            x = k == kCsMaxTs ? (y > x ? y : x) : k == kCsXor ? x ^ y : x + y;
-        }
-        if (lane == 0) sh[threadIdx.x >> 6][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < kCensusWords) {
-        const int k = threadIdx.x;
-        unsigned long long x = sh[0][k];
-        for (int w = 1; w < kCensusBlock / 64; ++w) {
-            const unsigned long long y = sh[w][k];
-            x = k == kCsMaxTs ? (y > x ? y : x) : k == kCsXor ? x ^ y : x + y;
-        }
-        if (x) {   // (0 is neutral for all three)
-            if (k == kCsMaxTs) atomicMax(&out[k], x);
-            else if (k == kCsXor) atomicXor(&out[k], x);
-            else atomicAdd(&out[k], x);
-        }
-    }
+    block_reduce<kCsMaxTs, kCsXor>(r, out);
 }
 
 int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
@@ -429,32 +445,17 @@ int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *
     if (g.entry_size % 64 || (line && g.entry_size != 64)) return -1;
     if (hipMemsetAsync(out, 0, kCensusWords * sizeof(unsigned long long), s) != hipSuccess) return -2;
     const uint32_t chunks = g.entry_size / 64;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    // A persistent grid striding over the table: as many blocks per CU as the instance's registers let the CU
-    // hold at once, so the blocks all start together and end together (a grid that needs a second, partial
-    // round of blocks ends with idle CUs). HKV_CENSUS_BLOCKS_PER_CU overrides it (timing experiments); no block
-    // waits for another, so any grid gives the same result.
+    // HKV_CENSUS_BLOCKS_PER_CU sets the grid's blocks per CU instead of the occupancy query (timing experiments)
     static const int env_bpc = getenv("HKV_CENSUS_BLOCKS_PER_CU") ? atoi(getenv("HKV_CENSUS_BLOCKS_PER_CU")) : 0;
-    int bpc = env_bpc;
-    if (bpc <= 0) {
-        const void *fn = line ? (const void *)k_table_census<true, false>
-                       : chunks > 1 ? (const void *)k_table_census<false, true> : (const void *)k_table_census<false, false>;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kCensusBlock, 0) != hipSuccess || bpc <= 0) bpc = 4;
-    }
-    if (bpc > 8) bpc = 8;
-    const uint64_t tiles = (num_bkts + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock, cap = (uint64_t)cus * bpc;
-    const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kCensusBlock);
     if (!offender_cap) offender_keys = nullptr;
-    if (line)
-        hipLaunchKernelGGL((k_table_census<true, false>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
-                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
-    else if (chunks > 1)
-        hipLaunchKernelGGL((k_table_census<false, true>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
-                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
-    else
-        hipLaunchKernelGGL((k_table_census<false, false>), grid, block, 0, s, index, log, line, num_bkts, g.log_mask,
-                           g.log_head, g.log_cap, chunks, out, offender_keys, offender_cap);
+    with_instance(line != nullptr, chunks > 1, [&](auto il, auto big) {
+        const auto k = k_table_census<decltype(il)::value, decltype(big)::value>;
+        // with the override there is no occupancy query (fn NULL) and the cap is the blocks per CU, at most 8
+        const dim3 grid = persistent_grid(env_bpc > 0 ? nullptr : (const void *)k, num_bkts, kCensusBktsPerBlock, device,
+                                          env_bpc > 0 && env_bpc < 8 ? env_bpc : 8);
+        hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, num_bkts, g.log_mask, g.log_head, g.log_cap, chunks, out, offender_keys,
+                           offender_cap);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -463,30 +464,6 @@ int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *
 // as the 16-B chunks the census reads: lane q of a group of four holds bytes 16q..16q+15 of an entry's first 64 B
 // (q = 1: the meta -- state, ts cid, ts version; q = 2, 3: the value from byte 33 on), and a 320-B entry's other
 // 256 B are value only.
-namespace {
-// N per-thread counts -> out[0..N): per wave by shuffles, per block through LDS, one atomic per non-zero field and
-// block. Every thread of the block calls it.
-template <int N>
-__device__ __forceinline__ void block_add(const uint32_t (&c)[N], unsigned long long *out)
-{
-    __shared__ unsigned long long sh[kCensusBlock / 64][N];
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        unsigned long long x = c[k];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
-        if (lane == 0) sh[threadIdx.x >> 6][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < N) {
-        unsigned long long x = 0;
-        for (int w = 0; w < kCensusBlock / 64; ++w) x += sh[w][threadIdx.x];
-        if (x) atomicAdd(&out[threadIdx.x], x);
-    }
-}
-}  // namespace
-
 // The census's pass over the buckets [bkt_lo, bkt_hi): every live slot whose timestamp is at least min_ts leaves
 // as one record. A block step takes kExtractK buckets per group of four lanes (512 per block) in three parts:
 // count (which slots qualify -- from the buckets alone when min_ts is 0, else with each entry's meta), reserve
@@ -495,6 +472,7 @@ __device__ __forceinline__ void block_add(const uint32_t (&c)[N], unsigned long 
 // wave and step, as the census's offender list takes, was measured first: every one of them lands on the same
 // address, about 25M of them for 100M keys, and the extract took 258 ms (profiles/repair_100m.txt).
 constexpr int kExtractK = 8;
+constexpr uint64_t kExtractBktsPerStep = (uint64_t)kCensusBktsPerBlock * kExtractK;   // buckets of one block step
 template <bool IL, bool BIG>
 __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *__restrict__ index,
                                                                 const uint8_t *__restrict__ log,
@@ -505,45 +483,40 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *_
                                                                 unsigned long long *result)
 {
     const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3, wave = threadIdx.x >> 6;
-    constexpr uint64_t kSuper = (uint64_t)kCensusBktsPerBlock * kExtractK;   // buckets of one block step
-    const uint64_t tiles = (bkt_hi - bkt_lo + kSuper - 1) / kSuper;
+    const uint64_t tiles = (bkt_hi - bkt_lo + kExtractBktsPerStep - 1) / kExtractBktsPerStep;
     __shared__ unsigned long long s_wtot[kCensusBlock / 64], s_base;
     uint32_t n_scanned[1] = {0};
-    // the digest's mask on this lane's two words of an entry's first 64 B (as in k_table_census)
-    const uint64_t mask_a = q == 0 ? 0ull : q == 1 ? 0xFF00000000FF0000ull : q == 2 ? 0xFFFFFFFFFFFFFF00ull : ~0ull;
-    const uint64_t mask_b = q == 1 ? 0x00000000FFFFFFFFull : ~0ull;
+    const uint64_t mask_a = digest_mask_a(q), mask_b = digest_mask_b(q);
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
-        const uint64_t b0 = bkt_lo + tile * kSuper + (threadIdx.x >> 2);   // (the four lanes of a group share it)
+        const uint64_t b0 = bkt_lo + tile * kExtractBktsPerStep + (threadIdx.x >> 2);   // (the four lanes of a group share it)
         // count: which slots of the group's kExtractK buckets leave as records (bit 8k + j: slot j of bucket k)
         uint4 v[kExtractK];
 #pragma unroll
         for (int k = 0; k < kExtractK; ++k) {
             const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
             v[k] = make_uint4(0u, 0u, 0u, 0u);
-            if (b < bkt_hi) v[k] = reinterpret_cast<const uint4 *>(IL ? line + b * 128u : index + b * 64u)[q];
+            if (b < bkt_hi) v[k] = (IL ? line_words(line, b) : bucket_words(index, b))[q];
         }
         uint64_t qm = 0;
 #pragma unroll
         for (int k = 0; k < kExtractK; ++k) {
             const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
             const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
-            const uint64_t o0 = (s0 >> 24) & ~(IL ? kInlineOffBit : 0ull), o1 = (s1 >> 24) & ~(IL ? kInlineOffBit : 0ull);
-            // in use and inside the log window (the lookup's check); an idle group's words are zero
-            const uint32_t g0 = (uint32_t)(__ballot((s0 & 1u) && log_head - o0 < log_cap) >> gbase) & 0xFu;
-            const uint32_t g1 = (uint32_t)(__ballot((s1 & 1u) && log_head - o1 < log_cap) >> gbase) & 0xFu;
-            uint32_t o = 0;   // bit 2*l + j: slot 2*l + j is live
-#pragma unroll
-            for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
+            // the live slots: in use and inside the log window; an idle group's words are zero
+            uint32_t o = group_slots(slot_in_use(s0) && in_log_window(log_head, log_cap, off_of<IL>(slot_off_raw(s0))),
+                                     slot_in_use(s1) && in_log_window(log_head, log_cap, off_of<IL>(slot_off_raw(s1))), gbase);
             if (q == 0) n_scanned[0] += __popc(o);
             if (min_ts) {   // (uniform) the filter needs each entry's timestamp: its bytes 16..31, the same for the four lanes
                 uint32_t left = o;
                 while (left) {   // (group-uniform)
                     const int j = __ffs(left) - 1;
                     left &= left - 1;
-                    const uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
-                    const uint4 m = (IL && (off & kInlineOffBit))
-                                        ? reinterpret_cast<const uint4 *>(line + b * 128u + 64u)[1]
-                                        : reinterpret_cast<const uint4 *>(log + ((off & ~(IL ? kInlineOffBit : 0ull)) & log_mask))[1];
+                    const uint64_t off = slot_off_raw(group_slot_word(s0, s1, j));
+                    // (line_entry_of_bucket written out, here and below: through the call the <true, false>
+                    // instance takes 104 VGPRs for 90 and loses a wave, profiles/table_dev_registers.txt)
+                    const uint4 m = off_is_inline<IL>(off)
+                                        ? reinterpret_cast<const uint4 *>(line + b * kLineBytes + kLineEntryOff)[1]
+                                        : reinterpret_cast<const uint4 *>(log + (off_of<IL>(off) & log_mask))[1];
                     if ((((uint64_t)m.z << 8) | (m.y >> 24)) < min_ts) o &= ~(1u << j);
                 }
             }
@@ -581,10 +554,10 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *_
             while (m8) {   // (group-uniform)
                 const int j = __ffs(m8) - 1;
                 m8 &= m8 - 1;
-                const uint64_t off = __shfl((j & 1) ? s1 : s0, j >> 1, 4) >> 24;
-                const uint4 *ent = (IL && (off & kInlineOffBit))
-                                       ? reinterpret_cast<const uint4 *>(line + b * 128u + 64u)
-                                       : reinterpret_cast<const uint4 *>(log + ((off & ~(IL ? kInlineOffBit : 0ull)) & log_mask));
+                const uint64_t off = slot_off_raw(group_slot_word(s0, s1, j));
+                const uint4 *ent = off_is_inline<IL>(off)
+                                       ? reinterpret_cast<const uint4 *>(line + b * kLineBytes + kLineEntryOff)
+                                       : reinterpret_cast<const uint4 *>(log + (off_of<IL>(off) & log_mask));
                 if (pos < record_cap) {
                     const uint4 c = ent[q];
                     const uint64_t wa = u64_of(c.x, c.y) & mask_a, wb = u64_of(c.z, c.w) & mask_b;
@@ -597,7 +570,7 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *_
             }
         }
     }
-    block_add<1>(n_scanned, result + 1);
+    block_reduce(n_scanned, result + 1);
 }
 
 // One record per group of four lanes, one pass: the lanes load the record's first 64 B and look its key up as
@@ -616,6 +589,8 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
                                                                 uint32_t kvs_value, uint32_t chunks,
                                                                 unsigned long long *result)
 {
+    Geometry g{};   // (the fields the probe reads)
+    g.bkt_mask = bkt_mask, g.log_mask = log_mask, g.log_head = log_head, g.log_cap = log_cap;
     const uint64_t E4 = BIG ? 4ull * chunks : 4ull;   // 16-B chunks of a record
     const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
     uint32_t cnt[4] = {0, 0, 0, 0};   // raised, equal, older, missed: lane 1 of a group counts for it
@@ -628,30 +603,18 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
         uint4 r = make_uint4(0u, 0u, 0u, 0u);
         if (live) r = records[i * E4 + q];
         const uint64_t key = __shfl(u64_of(r.z, r.w), 0, 4);
-        const uint64_t bkt = (key & 0xFFFFFFFFFFFFull) & bkt_mask;
+        const uint64_t bkt = bucket_of(g, key);
         uint4 v = make_uint4(0u, 0u, 0u, 0u), ev = v;
         if (live) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(IL ? line + bkt * 128u : index + bkt * 64u);
+            const uint4 *src = IL ? line_words(line, bkt) : bucket_words(index, bkt);
             v = src[q];
             if (IL) ev = src[4 + q];
         }
-        const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
-        const uint32_t tag = (uint32_t)(key >> 48);
-        const bool mt0 = live && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
-        const bool mt1 = live && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
-        const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu;
-        const uint32_t g1 = (uint32_t)(__ballot(mt1) >> gbase) & 0xFu;
-        uint32_t o = 0;   // bit 2*l + j: slot 2*l + j matches
-#pragma unroll
-        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
-        const int first = o ? __ffs(o) - 1 : 0;
-        uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
-        bool il = IL && (off & kInlineOffBit);
-        if (IL) off &= ~kInlineOffBit;
-        const bool ok = live && o && log_head - off < log_cap;
-        il = il && ok;
+        bool ok, il;
+        uint64_t phys;
+        group_probe<IL>(u64_of(v.x, v.y), u64_of(v.z, v.w), key, live, gbase, g, ok, phys, il);
         // where the entry's bytes live: the line's second half for the bucket's inline key, else the log
-        uint4 *home = reinterpret_cast<uint4 *>(il ? line + bkt * 128u + 64u : log + (off & log_mask));
+        uint4 *home = reinterpret_cast<uint4 *>(il ? line_entry_of_bucket(line, bkt) : log + phys);
         uint4 ln = make_uint4(0u, 0u, 0u, 0u);
         if (ok) ln = il ? ev : home[q];
         const bool hit = ok && __shfl(u64_of(ln.z, ln.w), 0, 4) == key;
@@ -703,7 +666,7 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
         cnt[2] += mine && d == kOlder;
         cnt[3] += mine && d == kMissed;
     }
-    block_add<4>(cnt, result);
+    block_reduce(cnt, result);
 }
 
 int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
@@ -714,27 +677,12 @@ int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t 
     if (hipMemsetAsync(result, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return -2;
     if (bkt_lo == bkt_hi) return 0;
     const uint32_t chunks = g.entry_size / 64;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 256;
-    // a persistent grid striding over the range, sized like the census's
-    const void *fn = line ? (const void *)k_table_extract<true, false>
-                   : chunks > 1 ? (const void *)k_table_extract<false, true> : (const void *)k_table_extract<false, false>;
-    int bpc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, fn, kCensusBlock, 0) != hipSuccess || bpc <= 0) bpc = 4;
-    if (bpc > 8) bpc = 8;
-    const uint64_t per_step = (uint64_t)kCensusBktsPerBlock * kExtractK;
-    const uint64_t tiles = (bkt_hi - bkt_lo + per_step - 1) / per_step, cap = (uint64_t)cus * bpc;
-    const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kCensusBlock);
-    uint4 *rec = reinterpret_cast<uint4 *>(records);
-    if (line)
-        hipLaunchKernelGGL((k_table_extract<true, false>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
-                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
-    else if (chunks > 1)
-        hipLaunchKernelGGL((k_table_extract<false, true>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
-                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
-    else
-        hipLaunchKernelGGL((k_table_extract<false, false>), grid, block, 0, s, index, log, line, bkt_lo, bkt_hi,
-                           g.log_mask, g.log_head, g.log_cap, chunks, min_ts, rec, record_cap, result);
+    with_instance(line != nullptr, chunks > 1, [&](auto il, auto big) {
+        const auto k = k_table_extract<decltype(il)::value, decltype(big)::value>;
+        const dim3 grid = persistent_grid((const void *)k, bkt_hi - bkt_lo, kExtractBktsPerStep, device, 8);
+        hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, bkt_lo, bkt_hi, g.log_mask, g.log_head, g.log_cap, chunks, min_ts,
+                           reinterpret_cast<uint4 *>(records), record_cap, result);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -746,23 +694,15 @@ int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, 
     if (g.entry_size % 64 || (line && big) || g.rmw_enabled) return -1;
     if (hipMemsetAsync(result, 0, 4 * sizeof(unsigned long long), s) != hipSuccess) return -2;
     if (!n) return 0;
-    int device = 0, cus = 0;
-    if (hipGetDevice(&device) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0)
-        cus = 256;
-    // as many blocks as the CUs hold at once (8 per CU at the instances' 8 waves per SIMD), striding over the records
-    const uint64_t blocks = (n + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock, cap = (uint64_t)cus * 8;
-    const dim3 grid((unsigned)(blocks < cap ? blocks : cap)), block(kCensusBlock);
-    const uint4 *rec = reinterpret_cast<const uint4 *>(records);
-    if (line)
-        hipLaunchKernelGGL((k_table_install<true, false>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
-                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
-    else if (big)
-        hipLaunchKernelGGL((k_table_install<false, true>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
-                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
-    else
-        hipLaunchKernelGGL((k_table_install<false, false>), grid, block, 0, s, index, log, line, rec, n, g.bkt_mask,
-                           g.log_mask, g.log_head, g.log_cap, g.kvs_value, chunks, result);
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) device = -1;   // (no device: the grid falls back to 256 CUs)
+    // 8 blocks per CU, what the CUs hold at once at the instances' 8 waves per SIMD: no occupancy query
+    const dim3 grid = persistent_grid(nullptr, n, kCensusBktsPerBlock, device, 8);
+    with_instance(line != nullptr, big, [&](auto il, auto bg) {
+        hipLaunchKernelGGL((k_table_install<decltype(il)::value, decltype(bg)::value>), grid, dim3(kCensusBlock), 0, s,
+                           index, log, line, reinterpret_cast<const uint4 *>(records), n, g.bkt_mask, g.log_mask,
+                           g.log_head, g.log_cap, g.kvs_value, chunks, result);
+    });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

@@ -9,6 +9,7 @@
 #include "../../include/hermeskv_workload.h"
 #include "hkv_codes.h"
 #include "hkv_internal.h"
+#include "hkv_table_dev.h"
 
 namespace hkv {
 
@@ -1364,19 +1365,19 @@ __global__ __launch_bounds__(256) void k_peer_compact(const uint32_t *ids, const
 template <bool FLAG = false>
 __device__ __forceinline__ uint64_t find_entry(const TableView &t, uint64_t key)
 {
-    const uint64_t *b = reinterpret_cast<const uint64_t *>(t.index + ((key & 0xFFFFFFFFFFFFULL) & t.g.bkt_mask) * 64u);
-    const uint32_t tag = (uint32_t)(key >> 48);
+    const uint64_t *b = reinterpret_cast<const uint64_t *>(bucket_words(t.index, bucket_of(t.g, key)));
+    const uint32_t tag = key_tag(key);
     bool lowest = true;
     for (int s = 0; s < 8; ++s) {
         const uint64_t slot = b[s];
-        if ((slot & 1u) && ((uint32_t)(slot >> 1) & 0x7FFFFFu) == tag) {
-            const uint64_t off = slot >> 24;
-            if (t.g.log_head - off >= t.g.log_cap) return ~0ull;
+        if (slot_matches(slot, tag)) {
+            const uint64_t off = slot_off_raw(slot);
+            if (!in_log_window(t.g, off)) return ~0ull;
             const uint64_t phys = off & t.g.log_mask;
             if (*reinterpret_cast<const uint64_t *>(t.log + phys + 8) != key) return ~0ull;
             return phys | (FLAG && lowest && t.g.log_cap <= kInlineMaxLog ? kPhysInline : 0ull);
         }
-        if (slot & 1u) lowest = false;
+        if (slot_in_use(slot)) lowest = false;
     }
     return ~0ull;
 }
@@ -1385,7 +1386,7 @@ __device__ __forceinline__ uint64_t find_entry(const TableView &t, uint64_t key)
 template <bool IL>
 __device__ __forceinline__ const uint8_t *located_entry(const TableView &t, uint64_t loc, uint64_t key)
 {
-    if (IL && (loc & kPhysInline)) return t.line + ((key & 0xFFFFFFFFFFFFULL) & t.g.bkt_mask) * 128u + 64u;
+    if (IL && (loc & kPhysInline)) return line_entry(t.line, t.g, key);
     return t.log + (loc & ~kPhysInline);
 }
 
@@ -1435,26 +1436,15 @@ __global__ __launch_bounds__(256) void k_peer_ts(TableView t, uint8_t *invs, uin
     for (int k = 0; k < kPeerTsPair; ++k) {
         live[k] = __shfl(live[k], 0, 4);
         key[k] = __shfl(key[k], 0, 4);
-        v[k] = live[k] ? reinterpret_cast<const uint4 *>(t.index + ((key[k] & 0xFFFFFFFFFFFFULL) & t.g.bkt_mask) * 64u)[q]
-                       : make_uint4(0u, 0u, 0u, 0u);
+        v[k] = live[k] ? bucket_words(t.index, bucket_of(t.g, key[k]))[q] : make_uint4(0u, 0u, 0u, 0u);
     }
     bool ok[kPeerTsPair];
     uint64_t phys[kPeerTsPair];
     U64x2w ln[kPeerTsPair];
 #pragma unroll
     for (int k = 0; k < kPeerTsPair; ++k) {
-        const uint64_t s0 = (uint64_t)v[k].x | ((uint64_t)v[k].y << 32), s1 = (uint64_t)v[k].z | ((uint64_t)v[k].w << 32);
-        const uint32_t tag = (uint32_t)(key[k] >> 48);
-        const bool mt0 = live[k] && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
-        const bool mt1 = live[k] && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
-        const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu, g1 = (uint32_t)(__ballot(mt1) >> gbase) & 0xFu;
-        uint32_t o = 0;  // bit 2*l + j: slot 2*l + j matches (the reference's slot order)
-#pragma unroll
-        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
-        const int first = o ? __ffs(o) - 1 : 0;
-        const uint64_t off = __shfl((first & 1) ? (s1 >> 24) : (s0 >> 24), first >> 1, 4);
-        ok[k] = live[k] && o && t.g.log_head - off < t.g.log_cap;
-        phys[k] = off & t.g.log_mask;
+        bool il;   // (the index holds no flagged slot)
+        group_probe<false>(u64_of(v[k].x, v[k].y), u64_of(v[k].z, v[k].w), key[k], live[k], gbase, t.g, ok[k], phys[k], il);
         // lane 0: entry bytes 0..15 (key at 8), lane 1: bytes 16..31 (version at 24)
         ln[k] = ok[k] && q < 2 ? reinterpret_cast<const U64x2w *>(t.log + phys[k])[q] : U64x2w{0, 0};
     }

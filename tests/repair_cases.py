@@ -69,6 +69,20 @@ def make_records(keys, states, ts_ver, ts_cid, sizes, salt):
     return rec.view(np.uint8).reshape(len(keys), sizes.entry)
 
 
+def collision_records(T, oracle, ts_ver):
+    """Records at (ts_ver, 1) for K, M and both fakes of tests/inline_cases.collision_keys -- the fakes are absent
+    and share a present key's bucket and tag -- and eight ordinary present keys; every third record INVALID.
+    Returns (records, K, M, fakes)."""
+    from tests import inline_cases as C
+    K, M, fakes = C.collision_keys(T)
+    assert all(oracle.lookup(int(f)) is None for f in fakes)
+    others = np.setdiff1d(T.keys[T.present][:12], [K, M])[:8]
+    keys = np.concatenate([np.array([K, M], dtype=np.uint64), fakes, others.astype(np.uint64)])
+    assert len(np.unique(keys)) == len(keys) == 12
+    states = np.where(np.arange(len(keys)) % 3 == 0, int(L.State.INVALID), int(L.State.VALID))
+    return make_records(keys, states, ts_ver, 1, L.DEFAULT, 23), K, M, fakes
+
+
 def _chunks(apply, btype, elems, mb):
     for lo in range(0, len(elems), BATCH):
         part = elems[lo:lo + BATCH].copy()

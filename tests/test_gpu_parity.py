@@ -246,6 +246,49 @@ def test_random_rounds_reference_entry_points(skew):
         d.set_skew(0)
 
 
+def test_tag_collisions_reference_entry_points():
+    """Absent keys with a present key's bucket and tag (bit 40 is in neither) through the drop-in entry point's
+    partitioned launch (k_hpart): one batch of 250 local ops, one of INVs and one of VALs over two present keys,
+    their fakes and 50 others, each replayed on an oracle copy of the default table byte for byte; every element on
+    a fake comes out MISS (no element is one the batch function skips)."""
+    from hermes_amd import kvs as K
+    K.spacetime_init(0)
+    d = K.HermesKV.default_table()
+    o = _oracle_from_device(d, 0)
+    keys = gen_keys(1_000_000)
+    rng = np.random.default_rng(20261020)
+    tsp = gen.TsPool(rng)
+    found = np.array([k for k in keys[rng.choice(1_000_000, size=80, replace=False)] if o.lookup(int(k)) is not None])
+    present, others = found[:2], found[2:52]
+    fakes = present ^ np.uint64(1 << 40)
+    assert len(others) == 50 and all(o.lookup(int(f)) is None for f in fakes)
+    pool = np.concatenate([present, fakes, others])      # (draw_keys favours the front of the pool)
+    mb = L.membership(5, 0)
+    loc = gen.local_ops(rng, pool, 250, L.DEFAULT, False, tsp)
+    loc["state"] = int(L.Bucket.NEW)
+    inv = gen.invs(rng, pool, 250, L.DEFAULT, False, tsp)
+    inv["opcode"] = int(L.Op.INV)
+    val = gen.vals(rng, pool, 250, L.DEFAULT, False, tsp)
+    for btype, e, what in ((L.BatchType.local_ops, loc, "local"), (L.BatchType.invs, inv, "invs"),
+                           (L.BatchType.vals, val, "vals")):
+        eo = gen.bytecopy(e)
+        on_fake = np.isin(e["key"], fakes)
+        ns_g = [-1]
+        K.hermes_batch_ops_to_KVS(btype, e, len(e), e.dtype.itemsize, mb, ns_g, None, 0)
+        ns_o = o.batch(btype, eo, mb)
+        assert_elems_equal(e, eo, what)
+        assert ns_g[0] == ns_o, f"{what}: node_suspected {ns_g[0]} vs {ns_o}"
+        state = e["state"] if "state" in e.dtype.names else e["sender"]
+        # (the seed is fixed, and draw_keys gives the pool's third and fourth keys about 12 % of the 250 draws: ~30)
+        assert on_fake.sum() >= 20 and (state[on_fake] == int(L.Resp.MISS)).all(), f"{what}: elements on the fakes"
+        assert (state[~on_fake] != int(L.Resp.MISS)).all(), f"{what}: a present key missed"
+    for k in pool:
+        off = o.lookup(int(k))
+        if off is not None:
+            assert np.array_equal(d.log_bytes(off, 64), o.log_bytes()[off:off + 64]), f"entry of {int(k):#x}"
+    assert d.take_error_flags() == 0
+
+
 # ------------------------------------------------------------------ randomized protocol rounds
 CONFIGS = [
     pytest.param(dict(rmw=False, big=False), id="default"),

@@ -167,6 +167,29 @@ def test_missing_key_is_a_miss(table_a):
     assert np.array_equal(b.index_bytes(), before[0]) and np.array_equal(CM.oracle_image(b, S)[1], before[1])
 
 
+@pytest.mark.parametrize("rounds", [0, 2])
+def test_tag_collision_records_miss(rounds):
+    """the inputs of tests/test_repair_gpu.py::test_install_tag_collisions on the oracle alone, on a fresh table and
+    after two protocol rounds: the two fakes' records miss (their INVs come back MISS), K and M take the records'
+    timestamp"""
+    from tests import inline_cases as C
+    o = C.make_oracle("S")
+    T = C.describe(o, "S")
+    if rounds:
+        C.case_rounds(C.OracleEngine(o), T, C.Rec(T.inline_keys), rounds=rounds, big=(1,), check_after=())
+    ver = (CM.census_model(*CM.oracle_image(o, S))["max_ts"] >> 8) + 10
+    records, K, M, fakes = RC.collision_records(T, o, ver)
+    assert RM.install_counts(o, records) == {"raised": len(records) - 2, "equal": 0, "older": 0, "missed": 2}
+    inv, _ = RM.records_to_batches(records, S)
+    probe = inv.copy()
+    o.batch(L.BatchType.invs, probe, L.membership(3, 0))
+    miss = probe["state"] == int(L.Resp.MISS)
+    assert miss.sum() == 2 and set(inv["key"][miss].tolist()) == set(fakes.tolist())
+    ent = _entries_by_key(CM.oracle_image(o, S))
+    for k in (K, M):
+        assert (int(ent[int(k)]["ts_ver"]), int(ent[int(k)]["ts_cid"])) == (ver, 1)
+
+
 def test_digest_link_and_batches(table_a):
     _, image, census, records = table_a
     assert len(records) == census["keys"]

@@ -149,16 +149,16 @@ def test_extract_fresh_populate(n_keys, num_bkts, log_cap, big):
 
 
 # ------------------------------------------------------------------ 2. extract, INLINE with stale logs
-def _inline_twelve(name):
-    """geometry A, INLINE, two protocol rounds of tests/inline_cases.py (twelve launches) and no export"""
+def _inline_twelve(name, geo="A"):
+    """geometry A (or `geo`), INLINE, two protocol rounds of tests/inline_cases.py (twelve launches) and no export"""
     from hermes_amd import kvs
     from hermes_amd.kvs import HermesKV
-    n_keys, bkts, cap = C.GEO["A"]
+    n_keys, bkts, cap = C.GEO[geo]
     kvs.HermesKV.default_flags = kvs.BATCH_ENGINE     # (the single-workgroup kernel has no inline instance)
     try:
         g = HermesKV(n_keys, bkts, cap)
-        o = C.make_oracle("A")
-        T = C.describe(o, "A")
+        o = C.make_oracle(geo)
+        T = C.describe(o, geo)
         assert g.prefer_layout(INLINE)
         m = Mirror(g, o, name, table_check="deferred")
         C.case_rounds(GpuEngine(m), T, C.Rec(T.inline_keys), rounds=2, big=(1,), check_after=())
@@ -324,6 +324,47 @@ def test_install_inline_with_stale_logs():
     lay = g.layout()
     assert lay["state"] == INLINE and lay["conversions"] == 1 and lay["inline_launches"] == 24, lay
     m.check_table("after the install and two more inline rounds")
+    assert g.take_error_flags() == 0
+
+
+# ------------------------------------------------------------------ 4b. install: records for absent keys that collide
+@pytest.mark.parametrize("layout", [LOG, INLINE])
+def test_install_tag_collisions(layout):
+    """Records for K (its bucket's inline key), M (a bucket-mate in slot 7) and their fakes -- absent keys with the
+    same bucket and tag, tests/inline_cases.collision_keys -- among ordinary keys, all newer than the table, on the
+    1000-key geometry: the fakes miss after the probe's tag match and window check, at the key compare; K and M
+    are raised; index and log equal the oracle twin that ran records_to_batches. LOG: a fresh target. INLINE:
+    between two inline rounds with no export, as test_install_inline_with_stale_logs."""
+    from hermes_amd import kvs
+    if layout == INLINE:
+        g, o, T, m = _inline_twelve("install collisions", geo="S")
+    else:
+        g, o, _ = make_pair(*C.GEO["S"])
+        T = C.describe(o, "S")
+    ver = (CM.census_model(*CM.oracle_image(o, L.DEFAULT))["max_ts"] >> 8) + 10
+    records, K, M, fakes = RC.collision_records(T, o, ver)
+    want = RM.install_counts(o, records)
+    assert want == {"raised": len(records) - 2, "equal": 0, "older": 0, "missed": 2}
+    before = g.layout()
+    res = g.install(torch.from_numpy(records.copy()).cuda())
+    assert res.host() == want
+    assert g.layout() == before, "the install moved the layout or its counters"
+    RM.apply_records(o, records, L.DEFAULT, L.membership(3, 0))
+    log = CM.oracle_image(o, L.DEFAULT)[1]
+    for k in (K, M):
+        e = o.lookup(int(k))
+        assert int.from_bytes(log[e + 24:e + 28].tobytes(), "little") == ver and int(log[e + 23]) == 1
+    if layout == INLINE:
+        kvs.HermesKV.default_flags = kvs.BATCH_ENGINE
+        try:
+            C.case_rounds(GpuEngine(m), T, C.Rec(T.inline_keys), rounds=2, big=(1,), check_after=(), seed=4242)
+        finally:
+            kvs.HermesKV.default_flags = 0
+        lay = g.layout()
+        assert lay["state"] == INLINE and lay["conversions"] == 1 and lay["inline_launches"] == 24, lay
+        m.check_table("after the install and two more inline rounds")
+    else:
+        assert_tables_equal(g, o, "install of the collision records")
     assert g.take_error_flags() == 0
 
 
