@@ -954,8 +954,8 @@ __global__ __launch_bounds__(BP) void k_resolve0(BatchArgs a)
     // what the non-mutating elements read the entry value from (bytes below 16 are never read)
     uint8_t *rentry = kStage ? reinterpret_cast<uint8_t *>(&sent[3 * threadIdx.x]) - 16 : entry_of(a, e);
     const uint32_t bytes = (uint32_t)cnt * (uint32_t)a.esz;  // a multiple of 8
-    // big ops (312 B): only the elements that hit move through LDS (message slabs are mostly
-    // padding); 8-B words, each inside one element
+    // big ops (56 + 64 c bytes for c extra cache lines: 312 B at c = 4, 1080 B at most): only the elements that
+    // hit move through LDS (message slabs are mostly padding); 8-B words, each inside one element
     constexpr bool kLive = BP == 128;
     __shared__ uint8_t live[kLive ? BP : 1];
     const uint32_t ew = (uint32_t)a.esz / 8u;
@@ -1025,8 +1025,11 @@ __global__ __launch_bounds__(BP) void k_resolve0(BatchArgs a)
         reinterpret_cast<uint64_t *>(dst)[bytes / 8 - 1] = reinterpret_cast<const uint64_t *>(sops)[bytes / 8 - 1];
 }
 
-// k_resolve0 for big ops (312 B) in place: one thread per element on its global copy, no LDS, so
-// occupancy is bound by registers instead of by 312 B of LDS per element (local and ACK launches)
+// k_resolve0 for big ops (any op of more than 64 B: 56 + 64 c bytes, 312 B at c = 4) in place: one thread per
+// element on its global copy, no LDS, so occupancy is bound by registers instead of by an op's bytes of LDS per
+// element (local and ACK launches). Values of at most 320 B are copied, and a key's first candidate applied to
+// its shadow, by the whole wave; larger ones by their own lane (the wave copies hold 64 lanes x 5 bytes, and
+// apply_to_shadow_wave's block copies were laid out for entries of a few lanes)
 // The value copies the wave's exec calls recorded (Ctx::vc), made by the whole wave: byte k of a
 // value by lane k % 64, so each instruction moves 64 consecutive bytes. kVcBatch values at a time:
 // all their loads are issued before the first store, so a wave waits one memory latency per
@@ -1170,6 +1173,7 @@ __device__ __forceinline__ void wave_value_copies(const VCopy &v, uint32_t n, in
 // instruction, and kBcRounds instructions' loads are issued before their stores. Every lane of the
 // wave calls it.
 constexpr int kBcRounds = 2;
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src);
 __device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *src, uint32_t bytes)
 {
     struct __attribute__((aligned(8))) W16 {
@@ -1177,9 +1181,23 @@ __device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *s
     };
     const int lane = threadIdx.x & 63;
     const int C = (int)((bytes + 15) / 16);
+    unsigned long long todo = __ballot(dst != nullptr);
+    if (C > 64) {   // more than 1024 B (1088-B entries): no copy fits one instruction, so the wave strides over
+                    // one copy at a time (per below would be 0 and the loop would never take a copy off todo)
+        while (todo) {
+            const int j = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            uint8_t *d = reinterpret_cast<uint8_t *>(shfl_u64((uint64_t)(uintptr_t)dst, j));
+            const uint8_t *sa = reinterpret_cast<const uint8_t *>(shfl_u64((uint64_t)(uintptr_t)src, j));
+            for (uint32_t o = 16u * (uint32_t)lane; o < bytes; o += 1024u) {
+                if (o + 16u > bytes) *reinterpret_cast<uint64_t *>(d + o) = *reinterpret_cast<const uint64_t *>(sa + o);
+                else *reinterpret_cast<W16 *>(d + o) = *reinterpret_cast<const W16 *>(sa + o);
+            }
+        }
+        return;
+    }
     const int per = 64 / C;
     const int slot = lane / C, ch = lane - slot * C;
-    unsigned long long todo = __ballot(dst != nullptr);
     while (todo) {
         W16 v[kBcRounds];
         uint8_t *dp[kBcRounds];

@@ -43,9 +43,10 @@ struct Geometry {
     uint64_t log_cap;
     uint64_t log_mask;
     uint64_t log_head;      // final head after populate (wrap check, hermesKV.c:969-970)
-    uint32_t entry_size;    // sizeof(struct mica_op): 64, or 320 with big objects
-    uint32_t st_value;      // ST_VALUE_SIZE: 31 or 287
-    uint32_t kvs_value;     // KVS_VALUE_SIZE: 46 or 302
+    // with big objects of c extra cache lines (c = 1..16; 4 is the reference's configs[2]) every size grows by 64 c
+    uint32_t entry_size;    // sizeof(struct mica_op): 64, or 64 + 64 c (320 at c = 4)
+    uint32_t st_value;      // ST_VALUE_SIZE: 31, or 31 + 64 c (287)
+    uint32_t kvs_value;     // KVS_VALUE_SIZE: 46, or 46 + 64 c (302)
     uint32_t shift;         // SHIFT_BITS
     uint32_t op_size;       // sizeof(spacetime_op_t)
     uint32_t entry_unit;    // divisor turning a physical log offset into a dense entry id

@@ -649,7 +649,9 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
             if (q == 3) nl = r;
         }
         if (hit && q > 0 && !(nl.x == ln.x && nl.y == ln.y && nl.z == ln.z && nl.w == ln.w)) home[q] = nl;
-        if (BIG && d == kRaised) {   // (320-B entries: four runs, their loads before their stores)
+        if (BIG && d == kRaised) {   // (the value's 64-B runs after the first, chunks - 1 of them, four at a time with
+                                     // their loads before their stores: 320-B entries have exactly four, other sizes
+                                     // end with a group of one to three)
             for (uint32_t k0 = 1; k0 < chunks; k0 += 4) {
                 uint4 t[4];
 #pragma unroll

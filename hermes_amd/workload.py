@@ -273,9 +273,13 @@ class Round:
         can_fuse = not coalesce_hot and val_credits is None and patchable(kvs.sizes)
         pays = kvs.sizes.op <= 64 or not retry_stalled
         self.fused = (can_fuse and pays) if fused_refill is None else (fused_refill and can_fuse)
-        # otherwise 312-B ops are refilled in place, but from the same state mirror (hkv_wl_refill_st), so a
-        # slot the refill keeps is not read
-        self.st_refill = not self.fused and not coalesce_hot and val_credits is None and self.op > 64
+        # otherwise big ops are refilled in place, but from the same state mirror (hkv_wl_refill_st), so a
+        # slot the refill keeps is not read -- where hkv_wl_refill_st takes the size: one wave writes an op's
+        # value, 64 words of 8 B at most (values up to 463 B). Bigger ops (479 B and more) go through
+        # hkv_wl_refill's LDS slab like small ones.
+        st_words = (L.OP_VALUE_OFF - 16 + kvs.sizes.st_value) // 8 + 7
+        self.st_refill = (not self.fused and not coalesce_hot and val_credits is None and self.op > 64
+                          and st_words <= 64)
         self.machine_id = kvs.machine_id
         dev = torch.device("cuda", kvs.device)
         W, S = n_workers, self.LOCAL

@@ -90,7 +90,14 @@ typedef struct hkv_config {
     uint32_t machine_id;        /* reference global machine_id (hrd.h:87) */
     uint32_t rmw_enabled;       /* ENABLE_RMWs (config.h:37) */
     uint32_t big_objects;       /* USE_BIG_OBJECTS (hrd.h:36) */
-    uint32_t extra_cache_lines; /* EXTRA_CACHE_LINES (hrd.h:37) */
+    uint32_t extra_cache_lines; /* EXTRA_CACHE_LINES (hrd.h:37). With big_objects: 1..16 accepted (values of
+                                   31 + 64 c bytes in entries of 64 + 64 c: 95 B / 128 B up to 1055 B / 1088 B);
+                                   anything else is refused by hkv_table_create. Without: ignored. The test suite
+                                   holds c = 1, 2, 4, 5, 8 and 16 to the reference byte for byte, on every batch
+                                   type and on census, extract and install (and c = 7 in the workload round). Only
+                                   c = 4 (287-B values, the reference's configs[2]) has kernel instances of its
+                                   own; every other c runs the general instances, correct at any accepted size,
+                                   with no speed claim made for them */
     int32_t  device;            /* HIP device ordinal */
     uint32_t rw_len;            /* elements of read_write_ops (max_batch_size, default 250) */
     uint32_t skew_flags;        /* HKV_SKEW_*: the reference's opt-in skew optimisations (0 = off,

@@ -17,9 +17,11 @@ def image(o, sizes=L.DEFAULT):
     return CM.oracle_image(o, sizes)
 
 
-def populated(n, bkts, cap, big=False, rmw=False, runs=None):
-    sizes = L.BIG if big else L.DEFAULT
-    o = OracleKVS(bkts, cap, 0, rmw, big, 4 if big else 0)
+def populated(n, bkts, cap, big=False, rmw=False, runs=None, ecl=None):
+    """ecl: big objects of that many extra cache lines (default: 4 with big, the default geometry without)"""
+    ecl = (4 if big else 0) if ecl is None else ecl
+    sizes = L.Sizes(True, ecl) if ecl else L.DEFAULT
+    o = OracleKVS(bkts, cap, 0, rmw, ecl > 0, ecl)
     for k in runs or (n,):
         o.populate(k, sizes.kvs_value)
     return o, sizes
@@ -41,18 +43,27 @@ def test_digest_is_keyed_by_key_not_by_position():
     assert ca["digest_sum"] and ca["digest_xor"]
 
 
-def _one_key(o, sizes):
-    key = int(gen_keys(300)[123])
+def _one_key(o, sizes, i=123):
+    key = int(gen_keys(i + 1)[i])
     off = o.lookup(key)
     assert off is not None
     return off
 
 
-@pytest.mark.parametrize("big", [False, True])
-def test_digest_sensitivity_and_insensitivity(big):
-    o, sizes = populated(500, 1024, 1 << 18, big=big, rmw=big)
+# the five big-object sizes of tests/test_value_sizes_gpu.py, each in a log that wraps (capacity below n * entry)
+SIZED_WRAPPED = [pytest.param(600, 1024, 1 << 16, False, 1, id="ecl1"), pytest.param(600, 1024, 1 << 16, False, 2, id="ecl2"),
+                 pytest.param(600, 1024, 1 << 17, False, 5, id="ecl5"), pytest.param(600, 1024, 1 << 18, False, 8, id="ecl8"),
+                 pytest.param(600, 1024, 1 << 19, False, 16, id="ecl16")]
+
+
+@pytest.mark.parametrize("n_keys,num_bkts,log_cap,big,ecl", [
+    pytest.param(500, 1024, 1 << 18, False, None, id="False"), pytest.param(500, 1024, 1 << 18, True, None, id="True"),
+    *SIZED_WRAPPED])
+def test_digest_sensitivity_and_insensitivity(n_keys, num_bkts, log_cap, big, ecl):
+    o, sizes = populated(n_keys, num_bkts, log_cap, big=big, rmw=big, ecl=ecl)
     idx, log, head, cap, _ = image(o, sizes)
     base = CM.census_model(idx, log, head, cap, sizes)
+    assert (ecl is None) == (head <= cap)                # (a wrapped log still holds the lowest ids)
     off = _one_key(o, sizes)
     dt = L.entry_dtype(sizes)
 
@@ -78,18 +89,21 @@ def test_digest_sensitivity_and_insensitivity(big):
         assert CM.digest(flipped(byte)) == CM.digest(base), what
     assert flipped(21)["obi_set"] == base["obi_set"] + 1          # (the counts do see obi)
     # two keys swapping their values is seen too (the sum is over keys, each hashed with its key)
-    off2 = o.lookup(int(gen_keys(300)[124]))
+    off2 = _one_key(o, sizes, 124)
     l2 = log.copy()
     assert log[off + 33] != log[off2 + 33]
     l2[off + 33], l2[off2 + 33] = log[off2 + 33], log[off + 33]
     assert CM.digest(CM.census_model(idx, l2, head, cap, sizes)) != CM.digest(base)
 
 
-@pytest.mark.parametrize("n_keys,num_bkts,log_cap,big", [(3000, 4096, 1 << 17, False), (2000, 1024, 1 << 18, True)])
-def test_wrapped_geometry_live_and_dead_slots(n_keys, num_bkts, log_cap, big):
-    """test_populate_bit_exact's wrapping geometries: the log has overwritten the oldest entries, their slots are
-    still in use; the census counts exactly the ids the lookup finds"""
-    o, sizes = populated(n_keys, num_bkts, log_cap, big=big, rmw=big)
+@pytest.mark.parametrize("n_keys,num_bkts,log_cap,big,ecl", [
+    pytest.param(3000, 4096, 1 << 17, False, None, id="3000-4096-131072-False"),
+    pytest.param(2000, 1024, 1 << 18, True, None, id="2000-1024-262144-True"), *SIZED_WRAPPED])
+def test_wrapped_geometry_live_and_dead_slots(n_keys, num_bkts, log_cap, big, ecl):
+    """test_populate_bit_exact's wrapping geometries, and one per big-object size: the log has overwritten the
+    oldest entries, their slots are still in use; the census counts exactly the ids the lookup finds"""
+    o, sizes = populated(n_keys, num_bkts, log_cap, big=big, rmw=big, ecl=ecl)
+    assert log_cap < n_keys * sizes.entry
     c = CM.census_model(*image(o, sizes))
     found = sum(o.lookup(int(k)) is not None for k in gen_keys(n_keys))
     assert c["dead_slots"] > 0

@@ -31,12 +31,13 @@ def _need_gpu():
         pytest.skip("no GPU")
 
 
-def make_pair(n_keys, num_bkts, log_cap, rmw=False, big=False, machine_id=0):
+def make_pair(n_keys, num_bkts, log_cap, rmw=False, big=False, machine_id=0, ecl=None):
+    """ecl: big objects of that many extra cache lines (default: 4 with big, the default geometry without)"""
     from hermes_amd.kvs import HermesKV
-    sizes = L.BIG if big else L.DEFAULT
-    ecl = 4 if big else 0
-    g = HermesKV(n_keys, num_bkts, log_cap, machine_id, rmw, big, ecl, populate=n_keys > 0)
-    o = OracleKVS(num_bkts, log_cap, machine_id, rmw, big, ecl)
+    ecl = (4 if big else 0) if ecl is None else ecl
+    sizes = L.Sizes(True, ecl) if ecl else L.DEFAULT
+    g = HermesKV(n_keys, num_bkts, log_cap, machine_id, rmw, ecl > 0, ecl, populate=n_keys > 0)
+    o = OracleKVS(num_bkts, log_cap, machine_id, rmw, ecl > 0, ecl)
     if n_keys:
         o.populate(n_keys, sizes.kvs_value)
     return g, o, sizes

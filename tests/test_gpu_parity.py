@@ -40,11 +40,12 @@ def _kvs():
     return HermesKV
 
 
-def make_pair(n_keys, num_bkts, log_cap, rmw=False, big=False, machine_id=0, skew=0):
-    sizes = L.BIG if big else L.DEFAULT
-    ecl = 4 if big else 0
-    g = _kvs()(n_keys, num_bkts, log_cap, machine_id, rmw, big, ecl, skew=skew)
-    o = OracleKVS(num_bkts, log_cap, machine_id, rmw, big, ecl, skew=skew)
+def make_pair(n_keys, num_bkts, log_cap, rmw=False, big=False, machine_id=0, skew=0, ecl=None):
+    """ecl: big objects of that many extra cache lines (default: 4 with big, the default geometry without)"""
+    ecl = (4 if big else 0) if ecl is None else ecl
+    sizes = L.Sizes(True, ecl) if ecl else L.DEFAULT
+    g = _kvs()(n_keys, num_bkts, log_cap, machine_id, rmw, ecl > 0, ecl, skew=skew)
+    o = OracleKVS(num_bkts, log_cap, machine_id, rmw, ecl > 0, ecl, skew=skew)
     o.populate(n_keys, sizes.kvs_value)
     return g, o, sizes
 
@@ -324,19 +325,25 @@ def _run_both(g, o, btype, elems_g, elems_o, mb, n_batches, stride, counts, rw_g
 
 @pytest.mark.parametrize("cfg", CONFIGS)
 def test_random_protocol_rounds(cfg):
+    random_protocol_rounds(cfg["rmw"], cfg["big"], cfg.get("skew", 0))
+
+
+def random_protocol_rounds(rmw, big, skew=0, ecl=None, observe=None, rounds=14, n_keys=3000):
+    """observe(kind, elems, oracle): called with every launch's elements after it. Returns the pair as the
+    last round left it: (device table, oracle, sizes)."""
     rng = np.random.default_rng(20261015)
-    rmw, big, skew = cfg["rmw"], cfg["big"], cfg.get("skew", 0)
-    n_keys, num_bkts = 3000, 512
-    sizes = L.BIG if big else L.DEFAULT
+    num_bkts = 512
+    sizes = L.Sizes(True, ecl) if ecl else L.BIG if big else L.DEFAULT
     log_cap = 1 << max(16, (n_keys * sizes.entry + 1024).bit_length())
-    g, o, sizes = make_pair(n_keys, num_bkts, log_cap, rmw=rmw, big=big, machine_id=0, skew=skew)
+    g, o, sizes = make_pair(n_keys, num_bkts, log_cap, rmw=rmw, big=big, machine_id=0, skew=skew, ecl=ecl)
+    observe = observe or (lambda kind, elems, oracle: None)
     assert_tables_equal(g, o, "populate")
     keys = gen_keys(n_keys)
     tsp = gen.TsPool(rng)
     mb_full = L.membership(5, 0)
     mb_fail = L.membership(5, 0, alive=0b01111)     # node 4 dropped
     W, S, M = 5, 48, 96                              # workers, local stride, message stride
-    for rnd in range(14):
+    for rnd in range(rounds):
         pool = gen.key_pool(rng, keys, hot=24 if rnd % 2 else 200)
         mb = mb_fail if rnd >= 9 else mb_full
         # local ops
@@ -351,6 +358,7 @@ def test_random_protocol_rounds(cfg):
         assert_elems_equal(loc, loc_o, f"round {rnd} local")
         gen.harvest_ts(tsp, loc)
         assert_tables_equal(g, o, f"round {rnd} local")
+        observe("local", loc, o)
         rw_g, rw_o = gen.bytecopy(loc), gen.bytecopy(loc)   # each worker's op buffer is its read_write_ops
         # invs
         inv = gen.invs(rng, pool, W * M, sizes, rmw, tsp)
@@ -362,6 +370,7 @@ def test_random_protocol_rounds(cfg):
         assert_elems_equal(inv, inv_o, f"round {rnd} invs")
         np.testing.assert_array_equal(ns_g, ns_o)
         assert_tables_equal(g, o, f"round {rnd} invs")
+        observe("invs", inv, o)
         # acks (read_write_ops = the local buffers)
         ack = gen.acks(rng, pool, W * M, sizes, rmw, tsp)
         counts = rng.integers(M // 2, M + 1, size=W).astype(np.int32)
@@ -370,6 +379,7 @@ def test_random_protocol_rounds(cfg):
         assert_elems_equal(ack, ack_o, f"round {rnd} acks")
         assert_elems_equal(rw_g, rw_o, f"round {rnd} acks rw")
         assert_tables_equal(g, o, f"round {rnd} acks")
+        observe("acks", ack, o)
         # vals
         val = gen.vals(rng, pool, W * M, sizes, rmw, tsp)
         val_o = gen.bytecopy(val)
@@ -383,6 +393,7 @@ def test_random_protocol_rounds(cfg):
             _run_both(g, o, L.BatchType.local_ops_after_membership_change, mem, mem_o, mb_fail, W, S, None)
             assert_elems_equal(mem, mem_o, f"round {rnd} membership")
             assert_tables_equal(g, o, f"round {rnd} membership")
+    return g, o, sizes
 
 
 def test_empty_and_all_miss_batches():
@@ -413,8 +424,12 @@ def test_empty_and_all_miss_batches():
 def test_max_size_batches_single_hot_key(cfg):
     """Maximum batch sizes (250 local / 900 msg per worker) all on one or two keys: every batch
     type goes through the hot-key workgroup engine (segments far longer than kShortSeg)."""
-    rmw, big = cfg["rmw"], cfg["big"]
-    g, o, sizes = make_pair(1000, 1024, 1 << 19 if big else 1 << 17, rmw=rmw, big=big)
+    max_size_batches_single_hot_key(cfg["rmw"], cfg["big"])
+
+
+def max_size_batches_single_hot_key(rmw, big, ecl=None):
+    sizes = L.Sizes(True, ecl) if ecl else L.BIG if big else L.DEFAULT
+    g, o, sizes = make_pair(1000, 1024, 1 << max(17, (1000 * sizes.entry + 1024).bit_length()), rmw=rmw, big=big, ecl=ecl)
     keys = gen_keys(1000)
     rng = np.random.default_rng(7)
     tsp = gen.TsPool(rng)
@@ -533,14 +548,19 @@ def test_inv_direct_path_edge_cases(big):
     to the first raise while the key is in WRITE), repeated maxima from several senders (the last
     one's sender is the last writer), INV_ABORT / OUT_OF_GROUP / MEMBERSHIP_CHANGE input opcodes,
     hot and missing keys, ragged counts, and launches past the 8192-element lookup head."""
-    g, o, sizes = make_pair(2000, 1024, 1 << 20 if big else 1 << 17, big=big)
+    inv_direct_path_edge_cases(big)
+
+
+def inv_direct_path_edge_cases(big, ecl=None, W=14, rounds=6):
+    sizes = L.Sizes(True, ecl) if ecl else L.BIG if big else L.DEFAULT
+    g, o, sizes = make_pair(2000, 1024, 1 << max(17, (2000 * sizes.entry + 1024).bit_length()), big=big, ecl=ecl)
     keys = gen_keys(2000)
     rng = np.random.default_rng(424242)
     tsp = gen.TsPool(rng)
     mb = L.membership(5, 0)
     e = sizes.entry
-    W, M = 14, 900
-    for rnd in range(6):
+    M = 900
+    for rnd in range(rounds):
         pool = gen.key_pool(rng, keys, hot=12 if rnd % 2 else 150)
         loc = gen.local_ops(rng, pool, 8 * 250, sizes, False, tsp)   # leaves keys in WRITE / REPLAY
         loc_o = gen.bytecopy(loc)
@@ -592,13 +612,18 @@ def test_ack_direct_path_edge_cases(big):
     oracle: ACKs matching each key's pending write or not, duplicate and out-of-range (>= 8)
     senders, quorums reached at different elements or never, LAST_ACK_* input opcodes, a
     membership with a dropped node, ragged counts and read_write_ops completions."""
-    g, o, sizes = make_pair(2000, 1024, 1 << 20 if big else 1 << 17, big=big)
+    ack_direct_path_edge_cases(big)
+
+
+def ack_direct_path_edge_cases(big, ecl=None, W=10, M=400, rounds=6):
+    sizes = L.Sizes(True, ecl) if ecl else L.BIG if big else L.DEFAULT
+    g, o, sizes = make_pair(2000, 1024, 1 << max(17, (2000 * sizes.entry + 1024).bit_length()), big=big, ecl=ecl)
     keys = gen_keys(2000)
     rng = np.random.default_rng(515151)
     tsp = gen.TsPool(rng)
-    W, S, M = 10, 250, 400
-    for rnd in range(6):
-        mb = L.membership(5, 0) if rnd < 4 else L.membership(5, 0, alive=0b10111)
+    S = 250
+    for rnd in range(rounds):
+        mb = L.membership(5, 0) if rnd < rounds - 2 else L.membership(5, 0, alive=0b10111)
         pool = gen.key_pool(rng, keys, hot=16 if rnd % 2 else 300)
         loc = gen.local_ops(rng, pool, W * S, sizes, False, tsp)     # pending writes / replays
         loc_o = gen.bytecopy(loc)
@@ -643,9 +668,12 @@ def test_scripted_rare_outcomes(cfg):
     (OUT_OF_GROUP, INV-aborts both ways, RMW_ABORT, ST_EMPTY reads, LAST_ACK completions of PUTs,
     RMWs and GET replays, write replays, *_COMPLETE_SEND_VALS after membership changes) all
     produced, covering every outcome code the batch function can emit in the build."""
+    scripted_rare_outcomes(cfg["rmw"], cfg["big"])
+
+
+def scripted_rare_outcomes(rmw, big, ecl=None):
     from tests.scripted import required_outcomes, run_scripted
-    rmw, big = cfg["rmw"], cfg["big"]
-    g, o, sizes = make_pair(1000, 4096, 1 << 22, rmw=rmw, big=big)
+    g, o, sizes = make_pair(1000, 4096, 1 << 22, rmw=rmw, big=big, ecl=ecl)
 
     def runner(btype, elems, mb, rw=None, node_suspected=None):
         eo, rwo = gen.bytecopy(elems), (gen.bytecopy(rw) if rw is not None else None)
@@ -726,10 +754,15 @@ def test_unique_inv_launch_matches_oracle(engine_path, rmw, big):
     equal and smaller timestamps, keys in WRITE (OUT_OF_GROUP), RMW INVs answered with INV-aborts,
     membership-change INVs (node_suspected), ragged counts and misses -- against the oracle; a slab
     with a repeated key raises error flag bit 4 (HKV_CHECK_UNIQUE, set by conftest)."""
+    unique_inv_launch_matches_oracle(engine_path, rmw, big)
+
+
+def unique_inv_launch_matches_oracle(engine_path, rmw, big, ecl=None):
     import os
     assert os.environ.get("HKV_CHECK_UNIQUE") == "1"
     rng = np.random.default_rng(4242)
-    g, o, sizes = make_pair(4000, 1024, 1 << 21 if big else 1 << 18, rmw=rmw, big=big)
+    sizes = L.Sizes(True, ecl) if ecl else L.BIG if big else L.DEFAULT
+    g, o, sizes = make_pair(4000, 1024, 1 << max(18, (4000 * sizes.entry + 1024).bit_length()), rmw=rmw, big=big, ecl=ecl)
     keys = gen_keys(4000)
     tsp = gen.TsPool(rng)
     mb = L.membership(5, 0)

@@ -102,6 +102,109 @@ def test_big_object_val_len_quirks():
     assert (ops["val_len"] == 244).all()
 
 
+# KVS_VALUE_SIZE = EXTRA_CACHE_LINES * 64 + 46 (hrd.h:36-47), ST_VALUE_SIZE = KVS_VALUE_SIZE - 15 (spacetime.h:29,
+# the 15-byte spacetime_object_meta), sizeof(struct mica_op) = 16 + 1 + 1 + KVS_VALUE_SIZE and sizeof(spacetime_op_t)
+# = 16 + 2 + ST_VALUE_SIZE (spacetime.h:170-185), both rounded up to their 8-byte alignment; worked out by hand
+VALUE_SIZES = {  # ecl: (kvs_value, st_value, entry, op)
+    1: (110, 95, 128, 120),
+    2: (174, 159, 192, 184),
+    5: (366, 351, 384, 376),
+    8: (558, 543, 576, 568),
+    16: (1070, 1055, 1088, 1080),
+}
+# The val_len bytes, all uint8 arithmetic with SHIFT_BITS 3, by hand per size:
+#   carried   what an op or INV carries and a replay writes into the op: ST_VALUE_SIZE >> 3 (hermesKV.c:20, 151)
+#   populated entry byte 17 after spacetime_populate_fixed_len(KVS_VALUE_SIZE): KVS_VALUE_SIZE >> 3 (spacetime.c:48)
+#   get_pop   op byte 10 after a GET of a populated key: (populated >> 3) - 16 (get_val_len, spacetime.h:263-267)
+#   put       entry byte 17 after a PUT: (carried >> 3) + 16 (set_val_len, spacetime.h:269-273; hermesKV.c:113)
+#   get_put   op byte 10 after a GET of that key: (put >> 3) - 16
+#   inv       entry byte 17 after a raising INV: (uint8_t) KVS_VALUE_SIZE (hermesKV.c:548)
+#   get_inv   op byte 10 after a GET of that key, validated: (inv >> 3) - 16
+VAL_LEN = {  # ecl: (carried, populated, get_pop, put, get_put, inv, get_inv)
+    1: (11, 13, 241, 17, 242, 110, 253),        # 95>>3; 110>>3; 1-16; 1+16; 2-16; 110; 13-16
+    2: (19, 21, 242, 18, 242, 174, 5),          # 159>>3; 174>>3; 2-16; 2+16; 2-16; 174; 21-16
+    5: (43, 45, 245, 21, 242, 110, 253),        # 351>>3; 366>>3; 5-16; 5+16; 2-16; 366-256; 13-16
+    8: (67, 69, 248, 24, 243, 46, 245),         # 543>>3; 558>>3; 8-16; 8+16; 3-16; 558-512; 5-16
+    16: (131, 133, 0, 32, 244, 46, 245),        # 1055>>3; 1070>>3; 16-16; 16+16; 4-16; 1070-1024; 5-16
+}
+
+
+@pytest.mark.parametrize("ecl", sorted(VALUE_SIZES))
+def test_value_size_derived_sizes(ecl):
+    """Sizes and the oracle's hko_*_size at the five big-object sizes the GPU suite runs, against literals"""
+    import ctypes
+    kvs_value, st_value, entry, op = VALUE_SIZES[ecl]
+    sz = L.Sizes(True, ecl)
+    assert (sz.kvs_value, sz.st_value, sz.entry, sz.op, sz.shift) == (kvs_value, st_value, entry, op, 3)
+    assert L.op_dtype(sz).itemsize == op and L.entry_dtype(sz).itemsize == entry
+    assert L.entry_dtype(sz).fields["value"][1] + st_value == 18 + kvs_value
+    cfg = O.Config(1, ecl, 0, 0, 1 << 8, 1 << 16, 0, 0)
+    got = []
+    for name in ("hko_kvs_value_size", "hko_st_value_size", "hko_entry_size", "hko_op_size"):
+        f = getattr(O.lib(), name)
+        f.restype, f.argtypes = ctypes.c_uint32, [ctypes.POINTER(O.Config)]
+        got.append(f(ctypes.byref(cfg)))
+    assert tuple(got) == VALUE_SIZES[ecl]
+
+
+@pytest.mark.parametrize("ecl", sorted(VAL_LEN))
+def test_value_size_val_len_bytes(ecl):
+    """entry byte 17 and op byte 10 after populate, a GET, a PUT, a raising INV and a write replay, per size"""
+    carried, populated, get_pop, put, get_put, inv_len, get_inv = VAL_LEN[ecl]
+    sz = L.Sizes(True, ecl)
+    kv = O.OracleKVS(1 << 10, 1 << 21, big_objects=True, extra_cache_lines=ecl)
+    kv.populate(1000, sz.kvs_value)
+    keys = O.gen_keys(1000)
+    mb = L.membership(3, 0)
+    k_put, k_inv, k_rep = (int(keys[i]) for i in (3, 4, 5))
+    assert carried == (sz.st_value >> sz.shift) & 0xFF
+
+    def byte17(key):
+        return int(kv.log_bytes()[kv.lookup(key) + 17])
+
+    def get(key, membership=mb):
+        op = np.zeros(1, dtype=L.op_dtype(sz))
+        op["key"], op["opcode"], op["state"] = key, int(L.Op.GET), int(L.Bucket.NEW)
+        kv.batch(L.BatchType.local_ops, op, membership)
+        return op[0]
+
+    assert byte17(k_put) == byte17(k_inv) == populated
+    g = get(k_put)
+    assert int(g["state"]) == int(L.Resp.GET_COMPLETE) and int(g["val_len"]) == get_pop
+    # a PUT: the entry takes set_val_len of what the op carries, the op's byte stays
+    p = np.zeros(1, dtype=L.op_dtype(sz))
+    p["key"], p["opcode"], p["state"], p["val_len"] = k_put, int(L.Op.PUT), int(L.Bucket.NEW), carried
+    p["value"] = 7
+    kv.batch(L.BatchType.local_ops, p, mb)
+    assert int(p["state"][0]) == int(L.Resp.PUT_SUCCESS) and int(p["val_len"][0]) == carried
+    assert byte17(k_put) == put
+    # ACKs from both peers validate it: the GET then reads get_val_len of the PUT's byte
+    ack = np.zeros(2, dtype=L.msg_dtype())
+    ack["key"], ack["opcode"], ack["sender"] = k_put, int(L.Op.ACK), [1, 2]
+    ack["ts_ver"], ack["ts_cid"] = p["ts_ver"][0], p["ts_cid"][0]
+    kv.batch(L.BatchType.acks, ack, mb, rw=p)
+    g = get(k_put)
+    assert int(g["state"]) == int(L.Resp.GET_COMPLETE) and int(g["val_len"]) == get_put and int(g["value"][-1]) == 7
+    # a raising INV: (uint8_t) KVS_VALUE_SIZE; its own byte stays; validated, a GET reads get_val_len of it
+    for key in (k_inv, k_rep):
+        inv = np.zeros(1, dtype=L.op_dtype(sz))
+        inv["key"], inv["opcode"], inv["state"], inv["val_len"] = key, int(L.Op.INV), 2, carried
+        inv["ts_ver"], inv["ts_cid"] = 2, 2
+        inv["value"] = 9
+        kv.batch(L.BatchType.invs, inv, mb)
+        assert int(inv["opcode"][0]) == int(L.Resp.INV_SUCCESS) and int(inv["val_len"][0]) == carried
+        assert byte17(key) == inv_len
+    val = np.zeros(1, dtype=L.msg_dtype())
+    val["key"], val["opcode"], val["sender"], val["ts_ver"], val["ts_cid"] = k_inv, int(L.Op.VAL), 2, 2, 2
+    kv.batch(L.BatchType.vals, val, mb)
+    g = get(k_inv)
+    assert int(g["state"]) == int(L.Resp.GET_COMPLETE) and int(g["val_len"]) == get_inv and int(g["value"][0]) == 9
+    # a GET of the key node 2 left INVALID, after node 2 was dropped: the write replay fills the op
+    r = get(k_rep, L.membership(3, 0, alive=0b011))
+    assert int(r["state"]) == int(L.Resp.REPLAY_SUCCESS) and int(r["val_len"]) == carried
+    assert (r["value"] == 9).all() and byte17(k_rep) == inv_len
+
+
 @pytest.mark.parametrize("rmw,big", [(False, False), (True, False), (True, True)])
 def test_scripted_rare_outcomes_oracle(rmw, big):
     """tests/scripted.py on the oracle alone: every branch outcome it expects (written out from

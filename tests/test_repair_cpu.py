@@ -53,7 +53,7 @@ def table_a():
 
 def _entries_by_key(image):
     entries, *_ = CM.live_entries(*image)
-    ent = entries.copy().view(L.entry_dtype(S)).reshape(-1)
+    ent = entries.copy().view(L.entry_dtype(image[4])).reshape(-1)
     return {int(e["key"]): e for e in ent}
 
 
@@ -64,10 +64,11 @@ def _expected_digest(records, image_b_before):
     for r in want.values():
         if r[18] != int(L.State.VALID):
             r[18] = int(L.State.INVALID)
+    sizes = image_b_before[4]
     entries, *_ = CM.live_entries(*image_b_before)
-    masked = entries & CM.digest_mask(S)[None, :]
+    masked = entries & CM.digest_mask(sizes)[None, :]
     exp = np.stack([want.get(int(m[8:16].copy().view("<u8")[0]), m) for m in masked])
-    h = CM.entry_hashes(exp, S)
+    h = CM.entry_hashes(exp, sizes)
     return int(h.sum(dtype=np.uint64)), int(np.bitwise_xor.reduce(CM.mix64(h + np.uint64(CM.G))))
 
 
@@ -76,10 +77,13 @@ def test_geometry_independence_idempotence(table_a):
     digest and a key the source caught mid-write arrives INVALID, so B's digest is A's with those keys' state byte
     INVALID (equal to A's outright once A is quiet: test_quiet_source_digest_equal)."""
     _, image_a, census_a, records = table_a
-    b = _table(2048, 1 << 19)
+    _independence_idempotence(image_a, census_a, records, _table(2048, 1 << 19), S)
+
+
+def _independence_idempotence(image_a, census_a, records, b, S):
     mb = L.membership(5, 0)
     image_b0 = CM.oracle_image(b, S)
-    counts = RM.install_counts(b, records)
+    counts = RM.install_counts(b, records, S)
     assert counts["raised"] > 0 and counts["equal"] > 0 and counts["older"] == 0
     RM.apply_records(b, records, S, mb)
     image_b = CM.oracle_image(b, S)
@@ -107,10 +111,36 @@ def test_geometry_independence_idempotence(table_a):
     assert census_b["by_state"][int(L.State.INVALID)] == n_not
     # idempotence: the same records again change no byte
     before = (b.index_bytes().copy(), image_b[1])
-    again = RM.install_counts(b, records)
+    again = RM.install_counts(b, records, S)
     assert again["raised"] == 0 and again["equal"] == counts["raised"] + counts["equal"]
     RM.apply_records(b, records, S, mb)
     assert np.array_equal(b.index_bytes(), before[0]) and np.array_equal(CM.oracle_image(b, S)[1], before[1])
+
+
+@pytest.mark.parametrize("ecl", [1, 2, 5, 8, 16])
+def test_geometry_independence_idempotence_value_sizes(ecl):
+    """The same at the five big-object sizes of tests/test_value_sizes_gpu.py: a source of 1500 keys in 2048
+    buckets whose log wraps (the capacity is the largest power of two below 1500 entries, so the highest ids, populated
+    first, are dead slots), scripted by tests/repair_cases.py over its lowest ids, into a fresh target of the same ids in
+    512 buckets and a log that does not wrap."""
+    sizes = L.Sizes(True, ecl)
+    n = 1500
+    cap = 1 << ((n * sizes.entry).bit_length() - 1)
+    assert cap < n * sizes.entry
+    a = OracleKVS(2048, cap, RC.SRC_ID, False, True, ecl)
+    a.populate(n, sizes.kvs_value)
+    keys = gen_keys(n)
+    assert a.lookup(int(keys[n - 1])) is None and cap // sizes.entry - 8 > RC.TW[1]   # the script's ids are live
+    RC.source_script(lambda bt, e, mb: a.batch_multi(bt, e, 1, len(e), None, mb), keys, sizes)
+    image_a = CM.oracle_image(a, sizes)
+    census_a = CM.census_model(*image_a)
+    assert census_a["dead_slots"] > 0 and 0 < census_a["keys"] < n
+    assert sum(1 for x in census_a["by_state"] if x) >= 4, census_a["by_state"]
+    records = RM.extract_model(image_a)
+    assert len(records) == census_a["keys"] and records.shape[1] == sizes.entry
+    b = OracleKVS(512, 1 << (n * sizes.entry + 2048).bit_length(), 0, False, True, ecl)
+    b.populate(n, sizes.kvs_value)
+    _independence_idempotence(image_a, census_a, records, b, sizes)
 
 
 def test_quiet_source_digest_equal():

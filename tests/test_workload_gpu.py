@@ -21,10 +21,17 @@ def _need_gpu():
         pytest.skip("no GPU")
 
 
-@pytest.mark.parametrize("theta,workers,cfg3,fused,retry", [
-    (0.99, 40, False, None, False), (0.0, 40, False, None, False), (0.99, 160, False, None, False),
-    (0.99, 40, True, None, False), (0.99, 40, True, False, False), (0.99, 40, True, True, True)])
-def test_bench_round_mirrored(theta, workers, cfg3, fused, retry):
+@pytest.mark.parametrize("theta,workers,cfg3,fused,retry,ecl", [
+    pytest.param(0.99, 40, False, None, False, 0, id="0.99-40-False-None-False"),
+    pytest.param(0.0, 40, False, None, False, 0, id="0.0-40-False-None-False"),
+    pytest.param(0.99, 160, False, None, False, 0, id="0.99-160-False-None-False"),
+    pytest.param(0.99, 40, True, None, False, 4, id="0.99-40-True-None-False"),
+    pytest.param(0.99, 40, True, False, False, 4, id="0.99-40-True-False-False"),
+    pytest.param(0.99, 40, True, True, True, 4, id="0.99-40-True-True-True"),
+    # other big-object sizes: 95-B values keep the planned patches; 479-B values are the first that the refill
+    # stages through an LDS slab of more than 64 KiB (hkv_wl_refill: 250 ops of 504 B) instead of in place
+    pytest.param(0.99, 40, True, None, False, 1, id="ecl1"), pytest.param(0.99, 40, True, None, False, 7, id="ecl7")])
+def test_bench_round_mirrored(theta, workers, cfg3, fused, retry, ecl):
     """cfg3: bench.py --config cfg3 (RMWs on, big objects, 25 % PUT + 25 % RMW): the rounds engine,
     op-sized ACKs from the virtual peers, RMW completions. Its refills are planned as patches that the
     local launch's in-place resolve writes (patch_in_resolve), or with fused=False refilled in place
@@ -35,13 +42,16 @@ def test_bench_round_mirrored(theta, workers, cfg3, fused, retry):
     n_keys, bkts = 60_000, 1 << 16
     cap = 1 << 25 if cfg3 else 1 << 23
     steps = 3                         # 10,000 / 40,000 local elements per launch
-    g = HermesKV(n_keys, bkts, cap, machine_id=0, rmw=cfg3, big_objects=cfg3, extra_cache_lines=4 if cfg3 else 0)
-    o = OracleKVS(bkts, cap, 0, cfg3, cfg3, 4 if cfg3 else 0)
+    g = HermesKV(n_keys, bkts, cap, machine_id=0, rmw=cfg3, big_objects=cfg3, extra_cache_lines=ecl)
+    o = OracleKVS(bkts, cap, 0, cfg3, cfg3, ecl)
     o.populate(n_keys, g.sizes.kvs_value)
+    assert g.sizes == L.Sizes(cfg3, ecl) and n_keys * g.sizes.entry < cap
     m = Mirror(g, o, "bench round")
     r = Round(g, workers, L.membership(3, 0), [1, 2], zipf_params(n_keys, theta), 500 if cfg3 else 200,
               500 if cfg3 else 0, seed=0x5EED, max_steps=8, trace_len=1024, fused_refill=fused, retry_stalled=retry)
-    assert r.fused == (fused is not False)   # (cfg3 under retry plans only when asked: fused=True)
+    # (cfg3 under retry plans only when asked: fused=True; values above 320 B take no patches in the resolve)
+    assert r.fused == (fused is not False and g.sizes.st_value <= 320)
+    assert r.st_refill == (cfg3 and not r.fused and ecl == 4)
     for _ in range(steps):
         r.step()
     torch.cuda.synchronize()
@@ -107,8 +117,11 @@ def test_merged_plan_peer_ts_equals_split(cfg3):
         assert g.take_error_flags() == 0
 
 
-@pytest.mark.parametrize("skew,rmw", [(0, True), (3, True), (3, False)])
-def test_big_patches_applied_in_resolve(skew, rmw):
+@pytest.mark.parametrize("skew,rmw,ecl", [
+    pytest.param(0, True, 4, id="0-True"), pytest.param(3, True, 4, id="3-True"), pytest.param(3, False, 4, id="3-False"),
+    # other sizes: up to 320 B the resolve takes the patches as at 287; above, k_apply_patch writes them first
+    *[pytest.param(skew, rmw, ecl, id=f"{skew}-{rmw}-ecl{ecl}") for ecl in (1, 5, 8) for skew, rmw in ((0, True), (3, False))]])
+def test_big_patches_applied_in_resolve(skew, rmw, ecl):
     """Refill patches of 312-B ops applied by the local launch itself (hkv_batch.hip patch_in_resolve:
     k_lookup reads each patch beside the op header, k_resolve0_direct runs the exec functions on a patched
     copy and writes the op once), against the oracle on the ops as the patches make them: every patch
@@ -121,9 +134,10 @@ def test_big_patches_applied_in_resolve(skew, rmw):
     from oracle.oracle import gen_keys
     from tests import gen
     n_keys, bkts, cap = 3000, 512, 1 << 21
-    g = HermesKV(n_keys, bkts, cap, machine_id=1, rmw=rmw, big_objects=True, extra_cache_lines=4, skew=skew)
-    o = OracleKVS(bkts, cap, 1, rmw, True, 4, skew=skew)
+    g = HermesKV(n_keys, bkts, cap, machine_id=1, rmw=rmw, big_objects=True, extra_cache_lines=ecl, skew=skew)
+    o = OracleKVS(bkts, cap, 1, rmw, True, ecl, skew=skew)
     o.populate(n_keys, g.sizes.kvs_value)
+    assert n_keys * g.sizes.entry < cap
     m = Mirror(g, o, "big patches")
     sz = g.sizes
     rng = np.random.default_rng(4242 + skew)
