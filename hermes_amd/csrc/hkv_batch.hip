@@ -1763,38 +1763,58 @@ __device__ __forceinline__ void local_resolve_nm(const BatchArgs &a, uint8_t *x,
     if (mut && a.error_flags) atomicOr(a.error_flags, 1u);
 }
 
-// Every element, F final (except on INVALID keys): see the section comment. One wave per block and
-// nothing shared beyond it. The lookup runs four lanes per element (each lane holds 16 B of the op
-// and of the log line); the wave-private LDS copies of op and entry are then resolved one element
-// per lane, so the exec code's branches are paid once per 32 elements; the ops go back whole.
+// F of the direct path: S_0 -> S_1 by the exec function on the element's own LDS copies of op (x) and entry
+// (ent, meta m) -- each element has a private copy of its entry, so the image nobody else reads becomes the
+// shadow's bytes, which the caller stores to shadow_of(a, i) whole (apply_to_shadow's result without its
+// byte accesses to global memory)
+__device__ __forceinline__ void local_first_lds(const BatchArgs &a, uint8_t *x, uint32_t i, uint8_t *ent, Meta m)
+{
+    Ctx c = make_ctx(a);
+    // the element's index in its batch (elem_at's, under 2^31 elements: 32-bit division)
+    const uint8_t idx = (uint8_t)(i - i / (uint32_t)a.stride * (uint32_t)a.stride);
+    if (x[8] == kOpGet) exec_read<31>(x, ent, idx, m, c);
+    else if (x[8] == kOpPut) exec_write<31>(x, ent, idx, m, c);
+    meta_store(ent, m);
+}
+
+// Every element, F final (except on INVALID keys): see the section comment. The lookup runs four
+// lanes per element (each lane holds 16 B of the op and of the log line); the LDS copies of op and
+// entry are then resolved one element per lane (see NW below); the ops go back whole.
 // Every hit's F word is loaded beside its log line; the word alone says whether this launch's prepass
 // offered a first candidate for the key (first_cand)
 // SGPR budget of k_local_fused, 80 (round 6: local launch 353-355 -> 341-351 us, 7 -> 8 waves per SIMD): waves are admitted
 // per SIMD by ~800 SGPRs / (ceil(sgpr/16) * 16 + 16) (MI355X_MICROARCH.md, "Residency"), so 92 SGPRs allow
 // 7 waves and 80 allow 8
-// NW waves per block (round 6): each wave works on its own 32 elements as before, and after the block's
+// NW waves per block (round 6): each wave loads, looks up and stages its own 32 elements, and after the block's
 // barrier the stage bytes and the state mirror of all NW * 32 elements go out as whole 64-byte blocks (a
 // wave's 32 bytes alone are half a block, which HBM writes with a read-modify-write: tools/calib_bench.hip,
 // 16-B random writes 2.4x the time of 64-B ones).
+// The resolve runs on full waves: between the barriers wave 0 resolves all 64 elements of the block, one per
+// lane, so the divergent exec code is issued once per 64 elements and not once per 32 on half-empty waves. A
+// key's first writer runs its exec function on its LDS copy of the entry (local_first_lds) and the wave then
+// stores the finished images to their shadows, 16 B per lane ("The fused pass's instructions").
 constexpr int kLfWaves = 2;   // waves per k_local_fused block
 template <int P, int NW, bool IL = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_sgpr(80))) void k_local_fused(BatchArgs a)
 {
     constexpr int E = 16 * P;   // elements per wave: P per lane group
     constexpr int EB = E * NW;  // elements per block
-    __shared__ uint4 sops_b[NW][E * 4];   // 64 B per op (56 used)
-    __shared__ uint4 sln_b[NW][E * 4];
-    __shared__ unsigned long long sfw_b[NW][E];
-    __shared__ uint32_t sent_b[NW][E];    // entry id of a hit, kNone otherwise
-    __shared__ uint8_t sprb_b[NW][E];     // probed (not skipped)
+    static_assert(EB == 64, "one wave resolves the block, one element per lane");
+    // per block element, each wave staging its own E
+    __shared__ uint4 sops_b[EB * 4];      // 64 B per op (56 used)
+    __shared__ uint4 sln_b[EB * 4];
+    __shared__ unsigned long long sfw_b[EB];
+    __shared__ uint32_t sent_b[EB];       // entry id of a hit, kNone otherwise
+    __shared__ uint8_t sprb_b[EB];        // probed (not skipped)
+    __shared__ uint8_t sfl[EB];           // the block's first writers (F), whose images go to their shadows
     __shared__ uint32_t sst[EB / 4], sstate[EB / 4];   // the block's stage bytes and state mirror
     __shared__ uint32_t sdef[EB];
     __shared__ uint32_t ndef;
     const int w = threadIdx.x >> 6, tid = threadIdx.x & 63, q = tid & 3, gbase = tid & ~3;
-    uint4 *sops = sops_b[w], *sln = sln_b[w];
-    unsigned long long *sfw = sfw_b[w];
-    uint32_t *sent = sent_b[w];
-    uint8_t *sprb = sprb_b[w];
+    uint4 *sops = sops_b + w * E * 4, *sln = sln_b + w * E * 4;
+    unsigned long long *sfw = sfw_b + w * E;
+    uint32_t *sent = sent_b + w * E;
+    uint8_t *sprb = sprb_b + w * E;
     const int64_t ib = (int64_t)blockIdx.x * EB, i0 = ib + (int64_t)w * E;
     if (threadIdx.x == 0) ndef = 0;
     uint64_t key[P];
@@ -1856,48 +1876,65 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_sgpr(80))) void 
         }
     }
     __syncthreads();
-    if (tid < E && i0 + tid < a.n && !HKV_DBG_ON(a, 64)) {
-        const int64_t i = i0 + tid;
-        uint8_t *x = reinterpret_cast<uint8_t *>(&sops[tid * 4]);
-        uint8_t *ent = reinterpret_cast<uint8_t *>(&sln[tid * 4]);
-        const uint32_t e = sent[tid];
+    // wave 0 resolves the block's EB elements, one per lane, on both waves' LDS copies: the exec code's
+    // branches are issued once per 64 elements; wave 1 waits at the barrier
+    if (__builtin_amdgcn_readfirstlane(w) == 0 && !HKV_DBG_ON(a, 64)) {
+        const int64_t i = ib + tid;
         uint8_t st = kStDone;
-        if (e != kNone) {
-            Ctx c = make_ctx(a);
-            Meta m;
-            meta_load(ent, m);
-            const bool wm = would_mutate(kLocal, x, m, c);
-            if (m_state(m) == kInvalid) {
-                // GET replays may mutate: they offer F now, and the key's elements resolve later
-                if (wm) {
-                    const uint64_t ph = phys_of(a, ent_id<IL>(e));
-                    offer(a.fw + fw_index(a, ph), a.rtag0, (uint32_t)i);
-                    if ((uint8_t)(m.w5 >> 16) != a.ltag)
-                        entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(x))[kEntryMetaOff + 4] = a.ltag;
-                }
-                st = kStDefer;
-                sdef[atomicAdd(&ndef, 1u)] = (uint32_t)i;
-            } else {
-                const uint32_t f = first_cand(sfw[tid], a.rtag0);
-                // a mutating element must have offered itself in k_local_pre
-                if (wm && (f == kNone || f > (uint32_t)i) && a.error_flags) atomicOr(a.error_flags, 4u);
-                if ((uint32_t)i == f) {
-                    apply_to_shadow<kLocal, 31>(a, x, (uint32_t)i, ent);
-                    st = kStCommit;
+        if (i < a.n) {
+            uint8_t *x = reinterpret_cast<uint8_t *>(&sops_b[tid * 4]);
+            uint8_t *ent = reinterpret_cast<uint8_t *>(&sln_b[tid * 4]);
+            const uint32_t e = sent_b[tid];
+            const bool prb = sprb_b[tid] != 0;
+            if (e != kNone) {
+                Meta m;
+                meta_load(ent, m);
+                Ctx c = make_ctx(a);
+                const bool wm = would_mutate(kLocal, x, m, c);
+                if (m_state(m) == kInvalid) {
+                    // GET replays may mutate: they offer F now, and the key's elements resolve later
+                    if (wm) {
+                        const uint64_t ph = phys_of(a, ent_id<IL>(e));
+                        offer(a.fw + fw_index(a, ph), a.rtag0, (uint32_t)i);
+                        if ((uint8_t)(m.w5 >> 16) != a.ltag)
+                            entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(x))[kEntryMetaOff + 4] = a.ltag;
+                    }
+                    st = kStDefer;
+                    sdef[atomicAdd(&ndef, 1u)] = (uint32_t)i;
                 } else {
-                    // F of a key that is not INVALID is its first PUT (k_local_pre)
-                    local_resolve_nm(a, x, ent, f != kNone && (uint32_t)i > f ? after_first<kLocal>(a, m, f, 1) : m);
+                    const uint32_t f = first_cand(sfw_b[tid], a.rtag0);
+                    // a mutating element must have offered itself in k_local_pre
+                    if (wm && (f == kNone || f > (uint32_t)i) && a.error_flags) atomicOr(a.error_flags, 4u);
+                    if ((uint32_t)i == f) {
+                        local_first_lds(a, x, (uint32_t)i, ent, m);
+                        st = kStCommit;
+                    } else {
+                        // F of a key that is not INVALID is its first PUT (k_local_pre)
+                        local_resolve_nm(a, x, ent, f != kNone && (uint32_t)i > f ? after_first<kLocal>(a, m, f, 1) : m);
+                    }
                 }
+            } else if (prb) {
+                x[9] = kMiss;
             }
-        } else if (sprb[tid]) {
-            x[9] = kMiss;
+            // k_local_pre read only the PUTs the caller's opcode mirror names
+            if (a.opc && prb && x[8] == kOpPut && a.opc[i] != kOpPut && a.error_flags) atomicOr(a.error_flags, 8u);
+            if (!HKV_DBG_ON(a, 1024)) a.ent[i] = e;
+            // a deferred element's state byte is written again by k_local_deferred, after this pass
+            reinterpret_cast<uint8_t *>(sst)[tid] = st;
+            reinterpret_cast<uint8_t *>(sstate)[tid] = x[9];
         }
-        // k_local_pre read only the PUTs the caller's opcode mirror names
-        if (a.opc && sprb[tid] && x[8] == kOpPut && a.opc[i] != kOpPut && a.error_flags) atomicOr(a.error_flags, 8u);
-        if (!HKV_DBG_ON(a, 1024)) a.ent[i] = e;
-        // a deferred element's state byte is written again by k_local_deferred, after this pass
-        reinterpret_cast<uint8_t *>(sst)[w * E + tid] = st;
-        reinterpret_cast<uint8_t *>(sstate)[w * E + tid] = x[9];
+        // the first writers' entry images, finished in LDS, go to their shadows: four lanes per image, 16 B
+        // each, 16 images per step
+        const unsigned long long fm = __ballot(st == kStCommit);
+        if (fm && !HKV_DBG_ON(a, 1024)) {
+            if (st == kStCommit) sfl[__popcll(fm & ((1ull << tid) - 1ull))] = (uint8_t)tid;
+            __threadfence_block();   // the images and the list, written by this wave's other lanes
+            const int nf = __popcll(fm);
+            for (int j = tid >> 2; j < nf; j += 16) {
+                const int t = sfl[j];
+                reinterpret_cast<uint4 *>(shadow_of(a, (uint32_t)(ib + t)))[q] = sln_b[t * 4 + q];
+            }
+        }
     }
     __syncthreads();
     // the block's stage bytes and state mirror as whole blocks (a partial last block byte by byte)
