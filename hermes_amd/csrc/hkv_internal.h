@@ -192,13 +192,23 @@ constexpr int kCensusWords = 25;   // sizeof(hkv_census) / 8
 int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
                         uint64_t num_bkts, unsigned long long *out, unsigned long long *offender_keys,
                         uint64_t offender_cap, int device, hipStream_t s);
+// The partitioned census (hermeskv.h "Partitioned census and delta repair"): the census's pass into
+// rows[p][0..3] = {digest_sum, digest_xor, keys, not VALID} of the live keys with key & (2^part_bits - 1) == p,
+// 2^part_bits <= num_bkts; overwritten (zeroed by the launch where its kernel adds to them). The rows' diff:
+// mask[p] = rows a and b differ in any word (accumulate: or-ed into mask[p]), *count = non-zero bytes of mask.
+int launch_table_census_parts(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                              uint64_t num_bkts, uint32_t part_bits, unsigned long long *rows, int device, hipStream_t s);
+int launch_part_rows_diff(const void *a, const void *b, uint32_t part_bits, uint8_t *mask, unsigned long long *count,
+                          int accumulate, int device, hipStream_t s);
 // Replica repair (hermeskv.h "Replica repair"). Extract: one pass like the census over the buckets [bkt_lo, bkt_hi)
 // -- of `line` when it is non-NULL, else of `index` -- that writes the masked entry image of every live slot whose
 // timestamp is at least min_ts to records (compacted, at most record_cap of them) and counts into
-// result[0] (records) and result[1] (scanned keys), which the launch zeroes first.
+// result[0] (records) and result[1] (scanned keys), which the launch zeroes first. part_sel (may be NULL: every
+// bucket): 2^part_bits bytes; a bucket b with part_sel[b & (2^part_bits - 1)] == 0 is neither loaded nor counted.
 int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
                          uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *records, uint64_t record_cap,
-                         unsigned long long *result, int device, hipStream_t s);
+                         unsigned long long *result, const uint8_t *part_sel, uint32_t part_bits, int device,
+                         hipStream_t s);
 // Install: n records, no key twice, applied as an INV and (source VALID) a VAL each to the entries of `log`, or,
 // with `line` non-NULL, to the lines for the inline keys; result[0..3] (raised, equal, older, missed) zeroed first.
 int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,

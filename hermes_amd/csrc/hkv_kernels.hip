@@ -311,6 +311,28 @@ __device__ __forceinline__ void block_reduce(const T (&v)[N], unsigned long long
     }
 }
 
+// The digest's h (hermeskv.h "Table census and digest") of the entry whose first 64 B the group of four lanes
+// holds -- lane q its words 2q (wa) and 2q + 1 (wb) -- and whose further 64-B runs (BIG) follow at ent: a lane
+// hashes the words it holds (the position salt makes that independent of the other lanes), the group adds up.
+// The same h in all four lanes.
+template <bool BIG>
+__device__ __forceinline__ uint64_t entry_hash(uint64_t wa, uint64_t wb, const uint4 *ent, int q, uint32_t chunks,
+                                               uint64_t mask_a, uint64_t mask_b)
+{
+    uint64_t e = mix64((wb & mask_b) + (uint64_t)(2 * q + 2) * kMixG);
+    if (q) e += mix64((wa & mask_a) + (uint64_t)(2 * q + 1) * kMixG);   // (word 0 is skipped)
+    if (BIG) {
+        for (uint32_t k = 1; k < chunks; ++k) {
+            const uint4 d = ent[4 * k + q];
+            const uint64_t i = 8ull * k + 2u * q;
+            e += mix64(u64_of(d.x, d.y) + (i + 1) * kMixG) + mix64(u64_of(d.z, d.w) + (i + 2) * kMixG);
+        }
+    }
+    e += __shfl_xor(e, 1, 4);
+    e += __shfl_xor(e, 2, 4);
+    return mix64(e);
+}
+
 // The passes' persistent grid: as many blocks per CU as the kernel's registers let a CU hold at once (at most cap;
 // fn NULL: cap itself), so the blocks all start and end together -- a grid that needs a second, partial round of
 // blocks ends with idle CUs. No block waits for another, so any grid gives the same result.
@@ -372,18 +394,7 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_census(const uint8_t *__
             const uint4 *ent = reinterpret_cast<const uint4 *>(log + (off & log_mask));
             const uint4 c = il ? iv : ent[q];
             const uint64_t wa = u64_of(c.x, c.y), wb = u64_of(c.z, c.w);
-            uint64_t e = mix64((wb & mask_b) + (uint64_t)(2 * q + 2) * kMixG);
-            if (q) e += mix64((wa & mask_a) + (uint64_t)(2 * q + 1) * kMixG);   // (word 0 is skipped)
-            if (BIG) {
-                for (uint32_t k = 1; k < chunks; ++k) {
-                    const uint4 d = ent[4 * k + q];
-                    const uint64_t i = 8ull * k + 2u * q;
-                    e += mix64(u64_of(d.x, d.y) + (i + 1) * kMixG) + mix64(u64_of(d.z, d.w) + (i + 2) * kMixG);
-                }
-            }
-            e += __shfl_xor(e, 1, 4);
-            e += __shfl_xor(e, 2, 4);
-            const uint64_t h = mix64(e);
+            const uint64_t h = entry_hash<BIG>(wa, wb, ent, q, chunks, mask_a, mask_b);
             const uint64_t key = __shfl(wb, 0, 4);
             // lane 1: wa = entry bytes 16..23, wb = 24..31
             const uint32_t state = (uint32_t)(wa >> 16) & 0xFFu, obi = (uint32_t)(wa >> 40) & 0xFFu,
@@ -459,6 +470,235 @@ int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// ------------------------------------------------------------------ the partitioned census
+// hermeskv.h "Partitioned census and delta repair": the census's digest_sum, digest_xor, keys and offenders per
+// partition p = key & (P - 1), P = 2^part_bits <= num_bkts, which is b & (P - 1) for every key of bucket b. Four
+// lanes per bucket with the census's loads and its liveness and residency rules (part_bucket below is that loop
+// with four sums); a row is four 64-bit words {sum, xor, keys, not VALID}. One atomic per bucket and field would
+// be 2^27 x 3 or 4 of them for the 100M-key table against ~22 G/s, so the sums have to meet on chip.
+//
+// Mapping A (k_table_census_parts, the default). A group of four lanes owns one partition for a whole unit of
+// work and walks the buckets b, b + S, b + 2S, ... with S = max(P, 64): they all lie in its partition, the sums
+// stay in registers, and a block step still reads 64 consecutive buckets. A unit is (a tile of 64 partitions, one
+// of `splits` pieces of the stride range); the blocks stride over the units. With P >= 64 and splits == 1 a row
+// has one owner, who writes it with two plain 16-B stores (lane 0: sum, xor; lane 1: keys, not VALID) -- no atomic
+// and no memset. Otherwise (P < 64: groups P apart share a partition; or too few tiles to fill the grid, so the
+// stride range is split over blocks) the groups add up per partition in LDS and the block sends at most four
+// atomics per partition and unit to rows the launch zeroed first.
+// Mapping B (k_table_census_parts_b, HKV_CENSUS_PARTS_MAPPING=B; kept for tools/delta_bench.py, which times it
+// beside A). The census's contiguous order. With P < 64 a group's partition is the same at every step, so it is
+// A's atomic path; with P >= 64 no two buckets of a step share a partition and every bucket's non-zero fields go
+// to the rows as atomics, one field per lane.
+// Measured (profiles/delta_100m.txt, 100M keys in 2^27 buckets, part_bits 12 / 16 / 20): A 6.10 / 6.14 / 6.12 ms
+// on a LOG table and 5.70 / 5.64 / 5.66 ms on an INLINE one, B 6.57 / 6.51 / 6.65 and 6.01 / 6.18 / 6.19 ms, the
+// census itself 7.69 and 7.82 ms in that session. A is faster at every size, its stride of 64 P bytes per step
+// (64 MiB at part_bits 20) costs nothing that shows, so A is the default.
+// Every field is a sum or an xor: any mapping, grid or split gives the same bytes.
+namespace {
+constexpr int kPartWords = 4;   // sizeof(hkv_part_row) / 8
+
+// bucket b's live keys into the group's sums: dsum, dxor and n_keys in all four lanes, n_nv in lane 1 (which
+// holds the state byte). live: b is a bucket of the table (the four lanes of a group share it).
+template <bool IL, bool BIG>
+__device__ __forceinline__ void part_bucket(const uint8_t *__restrict__ index, const uint8_t *__restrict__ log,
+                                            const uint8_t *__restrict__ line, uint64_t b, bool live, int q, int gbase,
+                                            uint64_t log_mask, uint64_t log_head, uint64_t log_cap, uint32_t chunks,
+                                            uint64_t mask_a, uint64_t mask_b, uint64_t &dsum, uint64_t &dxor,
+                                            uint32_t &n_keys, uint32_t &n_nv)
+{
+    uint4 v = make_uint4(0u, 0u, 0u, 0u), iv = v;
+    if (live) {
+        const uint4 *src = IL ? line_words(line, b) : bucket_words(index, b);
+        v = src[q];
+        if (IL) iv = src[4 + q];
+    }
+    const uint64_t s0 = u64_of(v.x, v.y), s1 = u64_of(v.z, v.w);
+    uint32_t o = group_slots(live && slot_in_use(s0), live && slot_in_use(s1), gbase);   // the slots in use
+    while (o) {   // (group-uniform)
+        const int j = __ffs(o) - 1;
+        o &= o - 1;
+        const uint64_t raw = slot_off_raw(group_slot_word(s0, s1, j)), off = off_of<IL>(raw);
+        if (!in_log_window(log_head, log_cap, off)) continue;   // the log has overwritten the entry
+        const uint4 *ent = reinterpret_cast<const uint4 *>(log + (off & log_mask));
+        const uint4 c = off_is_inline<IL>(raw) ? iv : ent[q];
+        const uint64_t wa = u64_of(c.x, c.y), wb = u64_of(c.z, c.w);
+        const uint64_t h = entry_hash<BIG>(wa, wb, ent, q, chunks, mask_a, mask_b);
+        ++n_keys;
+        n_nv += ((uint32_t)(wa >> 16) & 0xFFu) != kValid;   // lane 1: wa = entry bytes 16..23
+        dsum += h;
+        dxor ^= mix64(h + kMixG);
+    }
+}
+
+// The groups' sums of one unit, added up per partition in LDS (group gi's partition is slot gi & slot_mask of
+// sh), then at most four atomics per slot to rows[row0 + slot]. Every thread of the block calls it.
+__device__ __forceinline__ void part_rows_combine(unsigned long long (&sh)[kCensusBktsPerBlock * kPartWords], int q,
+                                                  uint32_t slot_mask, uint64_t dsum, uint64_t dxor, uint32_t n_keys,
+                                                  uint32_t n_nv, unsigned long long *rows, uint64_t row0)
+{
+    const uint32_t t = threadIdx.x;   // kCensusBlock threads: one per word of sh
+    sh[t] = 0;
+    __syncthreads();
+    if (q == 1 && n_keys) {
+        unsigned long long *r = sh + ((t >> 2) & slot_mask) * kPartWords;
+        atomicAdd(r + 0, (unsigned long long)dsum);
+        atomicXor(r + 1, (unsigned long long)dxor);
+        atomicAdd(r + 2, (unsigned long long)n_keys);
+        if (n_nv) atomicAdd(r + 3, (unsigned long long)n_nv);
+    }
+    __syncthreads();
+    // (thread t reads the word it zeroes at the next call: no barrier between the two is needed)
+    const unsigned long long x = sh[t];
+    if ((t >> 2) <= slot_mask && x) {
+        unsigned long long *dst = rows + (row0 + (t >> 2)) * kPartWords + (t & 3);
+        if ((t & 3) == 1) atomicXor(dst, x);
+        else atomicAdd(dst, x);
+    }
+}
+}  // namespace
+
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_census_parts(const uint8_t *__restrict__ index,
+                                                                     const uint8_t *__restrict__ log,
+                                                                     const uint8_t *__restrict__ line,
+                                                                     uint64_t num_bkts, uint64_t log_mask,
+                                                                     uint64_t log_head, uint64_t log_cap,
+                                                                     uint32_t chunks, uint32_t part_bits,
+                                                                     uint32_t splits, unsigned long long *rows)
+{
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    const uint32_t gi = threadIdx.x >> 2;
+    const uint64_t P = 1ull << part_bits, S = P > kCensusBktsPerBlock ? P : (uint64_t)kCensusBktsPerBlock;
+    const uint64_t ptiles = S / kCensusBktsPerBlock, K = (num_bkts + S - 1) / S, units = ptiles * splits;
+    const bool owner = P >= kCensusBktsPerBlock && splits == 1;   // (uniform) every row has one group
+    const uint64_t mask_a = digest_mask_a(q), mask_b = digest_mask_b(q);
+    __shared__ unsigned long long sh[kCensusBktsPerBlock * kPartWords];
+    for (uint64_t u = blockIdx.x; u < units; u += gridDim.x) {   // (block-uniform)
+        const uint64_t pt = u % ptiles, sp = u / ptiles;
+        const uint64_t k0 = K * sp / splits, k1 = K * (sp + 1) / splits;
+        const uint64_t first = pt * kCensusBktsPerBlock + gi;   // < S: the group's partition is first & (P - 1)
+        uint64_t dsum = 0, dxor = 0;
+        uint32_t n_keys = 0, n_nv = 0;   // (at most 8 (k1 - k0) <= num_bkts / 8 keys)
+        for (uint64_t k = k0; k < k1; ++k) {
+            const uint64_t b = first + k * S;
+            part_bucket<IL, BIG>(index, log, line, b, b < num_bkts, q, gbase, log_mask, log_head, log_cap, chunks,
+                                 mask_a, mask_b, dsum, dxor, n_keys, n_nv);
+        }
+        if (owner) {   // S == P and num_bkts is a multiple of it: first < P is a partition, and this group's alone
+            n_nv = __shfl(n_nv, 1, 4);
+            uint4 *row = reinterpret_cast<uint4 *>(rows + first * kPartWords);
+            if (q == 0) row[0] = make_uint4((uint32_t)dsum, (uint32_t)(dsum >> 32), (uint32_t)dxor, (uint32_t)(dxor >> 32));
+            if (q == 1) row[1] = make_uint4(n_keys, 0u, n_nv, 0u);
+        } else {
+            part_rows_combine(sh, q, (uint32_t)((P < kCensusBktsPerBlock ? P : (uint64_t)kCensusBktsPerBlock) - 1), dsum, dxor,
+                              n_keys, n_nv, rows, P < kCensusBktsPerBlock ? 0 : pt * kCensusBktsPerBlock);
+        }
+    }
+}
+
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_census_parts_b(const uint8_t *__restrict__ index,
+                                                                       const uint8_t *__restrict__ log,
+                                                                       const uint8_t *__restrict__ line,
+                                                                       uint64_t num_bkts, uint64_t log_mask,
+                                                                       uint64_t log_head, uint64_t log_cap,
+                                                                       uint32_t chunks, uint32_t part_bits,
+                                                                       unsigned long long *rows)
+{
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    const uint64_t P = 1ull << part_bits;
+    const bool shared = P < kCensusBktsPerBlock;   // (uniform) a group's partition is the same at every step
+    const uint64_t tiles = (num_bkts + kCensusBktsPerBlock - 1) / kCensusBktsPerBlock;
+    const uint64_t mask_a = digest_mask_a(q), mask_b = digest_mask_b(q);
+    __shared__ unsigned long long sh[kCensusBktsPerBlock * kPartWords];
+    uint64_t dsum = 0, dxor = 0;
+    uint32_t n_keys = 0, n_nv = 0;
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
+        const uint64_t b = tile * kCensusBktsPerBlock + (threadIdx.x >> 2);
+        part_bucket<IL, BIG>(index, log, line, b, b < num_bkts, q, gbase, log_mask, log_head, log_cap, chunks, mask_a,
+                             mask_b, dsum, dxor, n_keys, n_nv);
+        if (shared) continue;
+        n_nv = __shfl(n_nv, 1, 4);
+        const unsigned long long x = q == 0 ? dsum : q == 1 ? dxor : q == 2 ? n_keys : n_nv;   // a field per lane
+        if (x) {
+            unsigned long long *dst = rows + (b & (P - 1)) * kPartWords + q;
+            if (q == 1) atomicXor(dst, x);
+            else atomicAdd(dst, x);
+        }
+        dsum = dxor = 0;
+        n_keys = n_nv = 0;
+    }
+    if (shared) part_rows_combine(sh, q, (uint32_t)(P - 1), dsum, dxor, n_keys, n_nv, rows, 0);
+}
+
+int launch_table_census_parts(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                              uint64_t num_bkts, uint32_t part_bits, unsigned long long *rows, int device, hipStream_t s)
+{
+    const uint64_t P = 1ull << part_bits;
+    if (g.entry_size % 64 || (line && g.entry_size != 64) || part_bits > 63 || P > num_bkts) return -1;
+    const uint32_t chunks = g.entry_size / 64;
+    const char *env = getenv("HKV_CENSUS_PARTS_MAPPING");   // (read at every call: a tool times both in one process)
+    const bool map_b = env && (env[0] == 'B' || env[0] == 'b');
+    hipError_t zeroed = hipSuccess;
+    with_instance(line != nullptr, chunks > 1, [&](auto il, auto big) {
+        constexpr bool IL = decltype(il)::value, BIG = decltype(big)::value;
+        if (map_b) {
+            const auto k = k_table_census_parts_b<IL, BIG>;
+            zeroed = hipMemsetAsync(rows, 0, P * kPartWords * sizeof(unsigned long long), s);
+            if (zeroed != hipSuccess) return;
+            const dim3 grid = persistent_grid((const void *)k, num_bkts, kCensusBktsPerBlock, device, 8);
+            hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, num_bkts, g.log_mask, g.log_head, g.log_cap, chunks, part_bits, rows);
+            return;
+        }
+        const auto k = k_table_census_parts<IL, BIG>;
+        // the blocks the census would run on this table: what the units have to fill
+        const uint64_t full = persistent_grid((const void *)k, num_bkts, kCensusBktsPerBlock, device, 8).x;
+        const uint64_t S = P > kCensusBktsPerBlock ? P : (uint64_t)kCensusBktsPerBlock;
+        const uint64_t ptiles = S / kCensusBktsPerBlock, K = (num_bkts + S - 1) / S;
+        uint64_t splits = ptiles >= full ? 1 : (full + ptiles - 1) / ptiles;
+        if (splits > K) splits = K;
+        if (P < kCensusBktsPerBlock || splits > 1) {   // the rows are added to
+            zeroed = hipMemsetAsync(rows, 0, P * kPartWords * sizeof(unsigned long long), s);
+            if (zeroed != hipSuccess) return;
+        }
+        const uint64_t units = ptiles * splits;
+        hipLaunchKernelGGL(k, dim3((unsigned)(units < full ? units : full)), dim3(kCensusBlock), 0, s, index, log, line, num_bkts, g.log_mask, g.log_head,
+                           g.log_cap, chunks, part_bits, (uint32_t)splits, rows);
+    });
+    if (zeroed != hipSuccess) return -2;
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// d_mask[p] = the two rows differ (accumulate: or-ed into the byte that is there); count = the non-zero bytes
+// afterwards: one streaming pass, a thread per row, one atomic per block
+__global__ __launch_bounds__(kCensusBlock) void k_part_rows_diff(const uint4 *__restrict__ a, const uint4 *__restrict__ b,
+                                                                 uint64_t P, uint8_t *mask, unsigned long long *count,
+                                                                 int accumulate)
+{
+    uint32_t n[1] = {0};
+    for (uint64_t p = (uint64_t)blockIdx.x * kCensusBlock + threadIdx.x; p < P; p += (uint64_t)gridDim.x * kCensusBlock) {
+        const uint4 a0 = a[2 * p], a1 = a[2 * p + 1], b0 = b[2 * p], b1 = b[2 * p + 1];
+        const bool differ = ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) |
+                             (a1.z ^ b1.z) | (a1.w ^ b1.w)) != 0;
+        const uint8_t m = (uint8_t)((accumulate ? mask[p] : 0) | (differ ? 1 : 0));
+        mask[p] = m;
+        n[0] += m != 0;
+    }
+    block_reduce(n, count);
+}
+
+int launch_part_rows_diff(const void *a, const void *b, uint32_t part_bits, uint8_t *mask, unsigned long long *count,
+                          int accumulate, int device, hipStream_t s)
+{
+    if (part_bits > 63) return -1;
+    const uint64_t P = 1ull << part_bits;
+    if (hipMemsetAsync(count, 0, sizeof(unsigned long long), s) != hipSuccess) return -2;
+    const dim3 grid = persistent_grid(nullptr, P, kCensusBlock, device, 8);
+    hipLaunchKernelGGL(k_part_rows_diff, grid, dim3(kCensusBlock), 0, s, static_cast<const uint4 *>(a), static_cast<const uint4 *>(b), P, mask, count,
+                       accumulate);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 // ------------------------------------------------------------------ replica repair: extract and install
 // hermeskv.h "Replica repair". A record is the entry image under the digest's mask, so both kernels move entries
 // as the 16-B chunks the census reads: lane q of a group of four holds bytes 16q..16q+15 of an entry's first 64 B
@@ -471,16 +711,21 @@ int launch_table_census(const Geometry &g, const uint8_t *index, const uint8_t *
 // whole 64-B runs, 16 B per lane, the mask applied in registers; nothing at or past record_cap). One atomic per
 // wave and step, as the census's offender list takes, was measured first: every one of them lands on the same
 // address, about 25M of them for 100M keys, and the extract took 258 ms (profiles/repair_100m.txt).
+// MASKED (hkv_table_extract_parts_async): a bucket whose partition b & part_mask_of has a zero byte in part_sel is
+// not loaded and counts nowhere -- its words stay zero, as an idle group's. The selection bytes, 2 MiB at most,
+// stay in L2. A template parameter, so that the unmasked instances are the code they were.
 constexpr int kExtractK = 8;
 constexpr uint64_t kExtractBktsPerStep = (uint64_t)kCensusBktsPerBlock * kExtractK;   // buckets of one block step
-template <bool IL, bool BIG>
+template <bool IL, bool BIG, bool MASKED>
 __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *__restrict__ index,
                                                                 const uint8_t *__restrict__ log,
                                                                 const uint8_t *__restrict__ line, uint64_t bkt_lo,
                                                                 uint64_t bkt_hi, uint64_t log_mask, uint64_t log_head,
                                                                 uint64_t log_cap, uint32_t chunks, uint64_t min_ts,
                                                                 uint4 *__restrict__ records, uint64_t record_cap,
-                                                                unsigned long long *result)
+                                                                unsigned long long *result,
+                                                                const uint8_t *__restrict__ part_sel,
+                                                                uint64_t part_mask_of)
 {
     const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3, wave = threadIdx.x >> 6;
     const uint64_t tiles = (bkt_hi - bkt_lo + kExtractBktsPerStep - 1) / kExtractBktsPerStep;
@@ -495,7 +740,8 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *_
         for (int k = 0; k < kExtractK; ++k) {
             const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
             v[k] = make_uint4(0u, 0u, 0u, 0u);
-            if (b < bkt_hi) v[k] = (IL ? line_words(line, b) : bucket_words(index, b))[q];
+            if (b < bkt_hi && (!MASKED || part_sel[b & part_mask_of]))
+                v[k] = (IL ? line_words(line, b) : bucket_words(index, b))[q];
         }
         uint64_t qm = 0;
 #pragma unroll
@@ -673,17 +919,22 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
 
 int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
                          uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *records, uint64_t record_cap,
-                         unsigned long long *result, int device, hipStream_t s)
+                         unsigned long long *result, const uint8_t *part_sel, uint32_t part_bits, int device,
+                         hipStream_t s)
 {
     if (g.entry_size % 64 || (line && g.entry_size != 64) || bkt_lo > bkt_hi) return -1;
     if (hipMemsetAsync(result, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return -2;
     if (bkt_lo == bkt_hi) return 0;
     const uint32_t chunks = g.entry_size / 64;
+    const uint64_t part_mask_of = (1ull << part_bits) - 1;
     with_instance(line != nullptr, chunks > 1, [&](auto il, auto big) {
-        const auto k = k_table_extract<decltype(il)::value, decltype(big)::value>;
-        const dim3 grid = persistent_grid((const void *)k, bkt_hi - bkt_lo, kExtractBktsPerStep, device, 8);
-        hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, bkt_lo, bkt_hi, g.log_mask, g.log_head, g.log_cap, chunks, min_ts,
-                           reinterpret_cast<uint4 *>(records), record_cap, result);
+        const auto launch = [&](auto k) {
+            const dim3 grid = persistent_grid((const void *)k, bkt_hi - bkt_lo, kExtractBktsPerStep, device, 8);
+            hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, bkt_lo, bkt_hi, g.log_mask, g.log_head, g.log_cap, chunks, min_ts,
+                               reinterpret_cast<uint4 *>(records), record_cap, result, part_sel, part_mask_of);
+        };
+        if (part_sel) launch(k_table_extract<decltype(il)::value, decltype(big)::value, true>);
+        else launch(k_table_extract<decltype(il)::value, decltype(big)::value, false>);
     });
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -864,12 +864,17 @@ int hkv_copy_lines(hkv_table *t, void *dst, uint64_t off, uint64_t bytes)
 static_assert(sizeof(hkv_census) == kCensusWords * 8, "hkv_census and the kernel's word indices");
 uint32_t hkv_census_bytes(void) { return (uint32_t)sizeof(hkv_census); }
 
-int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender_keys, uint64_t offender_cap,
-                           void *stream)
+// What every pass over the table shares once its arguments are accepted (the census, the repair calls and the
+// partition calls): a live serving kernel is stopped, one caller at a time, ordered after the table's last stream
+// and the host-pointer path's, launch(line, s) with the lines of an INLINE table (else NULL) -- the table is read
+// where its truth lives, nothing is converted, no layout counter moves -- and `stream` becomes the last stream.
+// `detail` ends the call's trace line (its range or count; PASS_DETAIL formats it only when tracing).
+#define PASS_DETAIL(buf, ...) \
+    char buf[96] = "";        \
+    if (g_trace) snprintf(buf, sizeof buf, __VA_ARGS__)
+extern "C++" template <class Launch>
+static int table_pass(hkv_table *t, void *stream, const char *what, const char *detail, const Launch &launch)
 {
-    if (!t || !d_out) return fail(-1, "null argument");
-    if ((uintptr_t)d_out & 7) return fail(-1, "d_out must be 8-byte aligned");
-    if (offender_cap && !d_offender_keys) return fail(-1, "offender_cap without d_offender_keys");
     srv_stop(t);   // the serving kernel of the host-pointer path writes the table outside every stream order
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::mutex> lk(t->mu);   // against hkv_table_populate (geo.log_head)
@@ -877,14 +882,24 @@ int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender
     if (t->last_stream != s) HIP_TRY(hipStreamSynchronize(t->last_stream));
     if (t->stream != s) HIP_TRY(hipStreamSynchronize(t->stream));   // the host-pointer path's launches
     const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
-    if (int rc = launch_table_census(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr, t->cfg.num_bkts,
-                                     reinterpret_cast<unsigned long long *>(d_out),
-                                     reinterpret_cast<unsigned long long *>(d_offender_keys), offender_cap,
-                                     t->cfg.device, s))
-        return fail(-3, "census launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    if (int rc = launch(inl ? t->d_line : nullptr, s))
+        return fail(-3, "%s launch failed (%d): %s", what, rc, hipGetErrorString(hipGetLastError()));
     t->last_stream = s;
-    TRACE("census (%s)", inl ? "INLINE" : "LOG");
+    TRACE("%s (%s)%s", what, inl ? "INLINE" : "LOG", detail);
     return 0;
+}
+
+int hkv_table_census_async(hkv_table *t, hkv_census *d_out, uint64_t *d_offender_keys, uint64_t offender_cap,
+                           void *stream)
+{
+    if (!t || !d_out) return fail(-1, "null argument");
+    if ((uintptr_t)d_out & 7) return fail(-1, "d_out must be 8-byte aligned");
+    if (offender_cap && !d_offender_keys) return fail(-1, "offender_cap without d_offender_keys");
+    return table_pass(t, stream, "census", "", [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_census(t->geo, t->d_index, t->d_log, line, t->cfg.num_bkts,
+                                   reinterpret_cast<unsigned long long *>(d_out),
+                                   reinterpret_cast<unsigned long long *>(d_offender_keys), offender_cap, t->cfg.device, s);
+    });
 }
 
 int hkv_table_census(hkv_table *t, hkv_census *host_out)
@@ -916,52 +931,95 @@ static int repair_enter(hkv_table *t, const void *d_records, const void *d_resul
     return 0;
 }
 
-static int repair_order(hkv_table *t, hipStream_t s)
+// the extract's refusals, plain or masked, before anything is launched
+static int extract_enter(hkv_table *t, uint64_t bkt_lo, uint64_t bkt_hi, const void *d_records, uint64_t record_cap,
+                         const void *d_result, const char *what)
 {
-    HIP_TRY(hipSetDevice(t->cfg.device));
-    if (t->last_stream != s) HIP_TRY(hipStreamSynchronize(t->last_stream));
-    if (t->stream != s) HIP_TRY(hipStreamSynchronize(t->stream));   // the host-pointer path's launches
+    if (int rc = repair_enter(t, d_records, d_result, what)) return rc;
+    if (bkt_hi > t->cfg.num_bkts || bkt_lo > bkt_hi)
+        return fail(-1, "%s: bucket range [%llu, %llu) of %llu buckets", what, (unsigned long long)bkt_lo,
+                    (unsigned long long)bkt_hi, (unsigned long long)t->cfg.num_bkts);
+    if (record_cap && !d_records) return fail(-1, "%s: record_cap without d_records", what);
     return 0;
 }
 
 int hkv_table_extract_async(hkv_table *t, uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, void *d_records,
                             uint64_t record_cap, hkv_extract_result *d_result, void *stream)
 {
-    if (int rc = repair_enter(t, d_records, d_result, "extract")) return rc;
-    if (bkt_hi > t->cfg.num_bkts || bkt_lo > bkt_hi)
-        return fail(-1, "extract: bucket range [%llu, %llu) of %llu buckets", (unsigned long long)bkt_lo,
-                    (unsigned long long)bkt_hi, (unsigned long long)t->cfg.num_bkts);
-    if (record_cap && !d_records) return fail(-1, "extract: record_cap without d_records");
-    srv_stop(t);   // the serving kernel of the host-pointer path writes the table outside every stream order
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);   // against hkv_table_populate (geo.log_head)
-    if (int rc = repair_order(t, s)) return rc;
-    const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
-    if (int rc = launch_table_extract(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr, bkt_lo, bkt_hi, min_ts,
-                                      static_cast<uint8_t *>(d_records), record_cap,
-                                      reinterpret_cast<unsigned long long *>(d_result), t->cfg.device, s))
-        return fail(-3, "extract launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
-    t->last_stream = s;
-    TRACE("extract (%s) [%llu, %llu)", inl ? "INLINE" : "LOG", (unsigned long long)bkt_lo, (unsigned long long)bkt_hi);
-    return 0;
+    if (int rc = extract_enter(t, bkt_lo, bkt_hi, d_records, record_cap, d_result, "extract")) return rc;
+    PASS_DETAIL(d, " [%llu, %llu)", (unsigned long long)bkt_lo, (unsigned long long)bkt_hi);
+    return table_pass(t, stream, "extract", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_extract(t->geo, t->d_index, t->d_log, line, bkt_lo, bkt_hi, min_ts,
+                                    static_cast<uint8_t *>(d_records), record_cap,
+                                    reinterpret_cast<unsigned long long *>(d_result), nullptr, 0, t->cfg.device, s);
+    });
 }
 
 int hkv_table_install_async(hkv_table *t, const void *d_records, uint64_t n, hkv_install_result *d_result, void *stream)
 {
     if (int rc = repair_enter(t, d_records, d_result, "install")) return rc;
     if (n && !d_records) return fail(-1, "install: records without d_records");
-    srv_stop(t);
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(t->mu);
-    if (int rc = repair_order(t, s)) return rc;
-    const bool inl = t->layout_state == HKV_LAYOUT_INLINE;
-    if (int rc = launch_table_install(t->geo, t->d_index, t->d_log, inl ? t->d_line : nullptr,
-                                      static_cast<const uint8_t *>(d_records), n,
-                                      reinterpret_cast<unsigned long long *>(d_result), s))
-        return fail(-3, "install launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
-    t->last_stream = s;
-    TRACE("install (%s) %llu records", inl ? "INLINE" : "LOG", (unsigned long long)n);
+    PASS_DETAIL(d, " %llu records", (unsigned long long)n);
+    return table_pass(t, stream, "install", d, [&](uint8_t *line, hipStream_t s) {
+        return launch_table_install(t->geo, t->d_index, t->d_log, line, static_cast<const uint8_t *>(d_records), n,
+                                    reinterpret_cast<unsigned long long *>(d_result), s);
+    });
+}
+
+// Partitioned census and delta repair (hermeskv.h). The census's and the extract's rules, through table_pass.
+static_assert(sizeof(hkv_part_row) == 32, "the kernels' word indices");
+uint32_t hkv_part_row_bytes(void) { return (uint32_t)sizeof(hkv_part_row); }
+
+// part_bits <= log2(num_bkts): the rule that puts every key of a bucket into one partition
+static int part_bits_ok(const hkv_table *t, uint32_t part_bits, const char *what)
+{
+    if (part_bits > 63 || (1ull << part_bits) > t->cfg.num_bkts)
+        return fail(-1, "%s: part_bits %u: more partitions than the table's %llu buckets", what, part_bits,
+                    (unsigned long long)t->cfg.num_bkts);
     return 0;
+}
+
+int hkv_table_census_parts_async(hkv_table *t, uint32_t part_bits, hkv_part_row *d_rows, void *stream)
+{
+    if (!t || !d_rows) return fail(-1, "census_parts: null argument");
+    if ((uintptr_t)d_rows & 15) return fail(-1, "census_parts: d_rows must be 16-byte aligned");
+    if (int rc = part_bits_ok(t, part_bits, "census_parts")) return rc;
+    PASS_DETAIL(d, " part_bits %u", part_bits);
+    return table_pass(t, stream, "census_parts", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_census_parts(t->geo, t->d_index, t->d_log, line, t->cfg.num_bkts, part_bits,
+                                         reinterpret_cast<unsigned long long *>(d_rows), t->cfg.device, s);
+    });
+}
+
+int hkv_part_rows_diff_async(const hkv_part_row *d_a, const hkv_part_row *d_b, uint32_t part_bits, uint8_t *d_mask,
+                             uint64_t *d_count, int accumulate, void *stream)
+{
+    if (!d_a || !d_b || !d_mask || !d_count) return fail(-1, "part_rows_diff: null argument");
+    if (((uintptr_t)d_a | (uintptr_t)d_b) & 15) return fail(-1, "part_rows_diff: the rows must be 16-byte aligned");
+    if ((uintptr_t)d_count & 7) return fail(-1, "part_rows_diff: d_count must be 8-byte aligned");
+    if (part_bits > 48) return fail(-1, "part_rows_diff: part_bits %u", part_bits);   // (a bucket number has 48 bits)
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    if (int rc = launch_part_rows_diff(d_a, d_b, part_bits, d_mask, reinterpret_cast<unsigned long long *>(d_count),
+                                       accumulate, device, (hipStream_t)stream))
+        return fail(-3, "part_rows_diff launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+    return 0;
+}
+
+int hkv_table_extract_parts_async(hkv_table *t, uint32_t part_bits, const uint8_t *d_part_mask, uint64_t bkt_lo,
+                                  uint64_t bkt_hi, uint64_t min_ts, void *d_records, uint64_t record_cap,
+                                  hkv_extract_result *d_result, void *stream)
+{
+    if (int rc = extract_enter(t, bkt_lo, bkt_hi, d_records, record_cap, d_result, "extract_parts")) return rc;
+    if (!d_part_mask) return fail(-1, "extract_parts: null d_part_mask");
+    if (int rc = part_bits_ok(t, part_bits, "extract_parts")) return rc;
+    PASS_DETAIL(d, " part_bits %u [%llu, %llu)", part_bits, (unsigned long long)bkt_lo, (unsigned long long)bkt_hi);
+    return table_pass(t, stream, "extract_parts", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_extract(t->geo, t->d_index, t->d_log, line, bkt_lo, bkt_hi, min_ts,
+                                    static_cast<uint8_t *>(d_records), record_cap,
+                                    reinterpret_cast<unsigned long long *>(d_result), d_part_mask, part_bits,
+                                    t->cfg.device, s);
+    });
 }
 
 int hkv_hash_ids(const uint32_t *d_ids, uint64_t *d_keys_second, int64_t n, void *stream)

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .lib import ABI_VERSION, HkvBatchDesc, HkvCensus, HkvConfig, HkvLayoutInfo, Membership, check, raw
+from .lib import ABI_VERSION, HkvBatchDesc, HkvCensus, HkvConfig, HkvError, HkvLayoutInfo, Membership, check, raw
 
 _L = raw()
 
@@ -168,6 +168,25 @@ class Extract:
         """the written records as [written][E] uint8, in no particular order"""
         n = self.written
         return self.tensor[:n * self.entry].cpu().numpy().reshape(n, self.entry)
+
+
+PART_FIELDS = ("digest_sum", "digest_xor", "keys", "not_valid")   # hkv_part_row's words
+
+
+@dataclasses.dataclass
+class PartRows:
+    """The result of HermesKV.census_parts(), still on the device. `tensor`: [P, 4] int64, row p = hkv_part_row of
+    partition p (digest_sum, digest_xor, keys, not_valid: the unsigned words' bit patterns), P = 2^part_bits.
+    Nothing is read back until asked: field(name) is a device column for code that stays on the stream (a diff, a
+    collective, keys[mask].sum()); host() synchronises and returns the rows as uint64 [P, 4]."""
+    tensor: torch.Tensor
+    part_bits: int
+
+    def field(self, name: str) -> torch.Tensor:
+        return self.tensor[:, PART_FIELDS.index(name)]
+
+    def host(self) -> np.ndarray:
+        return self.tensor.cpu().numpy().view(np.uint64)
 
 
 INSTALL_FIELDS = ("raised", "equal", "older", "missed")
@@ -497,19 +516,50 @@ class HermesKV:
         check(_L.hkv_table_census(self.h, ctypes.byref(v)), "hkv_table_census")
         return _census_dict(bytes(v))
 
+    def census_parts(self, part_bits: int, out: torch.Tensor | None = None,
+                     stream: torch.cuda.Stream | None = None) -> "PartRows":
+        """hkv_table_census_parts_async: the census's digest_sum, digest_xor, keys and not-VALID count per partition
+        p = key & (2^part_bits - 1) of the live keys, as PartRows ([P, 4] int64 on the device, no host read), read
+        in one pass from whichever residency the table is in (nothing is converted), asynchronously on `stream`
+        (default: torch's current). part_bits <= log2(num_bkts), so that every key of a bucket lies in one partition;
+        a larger value is refused. The rows fold to census(): sums add, digest_xor xors. Equal tables, of any bucket
+        count, log order or residency, give equal rows. out: a contiguous int64 device tensor of 4 * 2^part_bits
+        words or more to write into (overwritten) instead of a new one. Tables with RMWs are accepted."""
+        part_bits = int(part_bits)
+        if not 0 <= part_bits < int(self.cfg.num_bkts).bit_length():
+            # more partitions than buckets: the library's refusal (it launches nothing), before 2^part_bits rows
+            # are asked of the allocator
+            row = torch.empty(4, dtype=torch.int64, device=torch.device("cuda", self.device))
+            check(_L.hkv_table_census_parts_async(self.h, part_bits & 0xFFFFFFFF, ctypes.c_void_p(row.data_ptr()),
+                                                  None), "hkv_table_census_parts_async")
+            raise HkvError(f"hkv_table_census_parts_async: part_bits {part_bits}")
+        P = 1 << part_bits
+        if out is None:
+            out = torch.empty(P * 4, dtype=torch.int64, device=torch.device("cuda", self.device))
+        assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() >= P * 4
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_census_parts_async(self.h, int(part_bits), ctypes.c_void_p(out.data_ptr()),
+                                              ctypes.c_void_p(s)), "hkv_table_census_parts_async")
+        return PartRows(out.view(-1)[:P * 4].view(P, 4), int(part_bits))
+
     # -- replica repair (include/hermeskv.h, "Replica repair")
     def extract(self, bkt_range: tuple[int, int] | None = None, min_ts: int = 0, out: torch.Tensor | None = None,
                 cap: int | None = None, stream: torch.cuda.Stream | None = None,
-                result: torch.Tensor | None = None) -> "Extract":
+                result: torch.Tensor | None = None, part_bits: int | None = None,
+                part_mask: torch.Tensor | None = None) -> "Extract":
         """hkv_table_extract_async: one record per live key of the buckets bkt_range = (lo, hi) (default: all) whose
         packed timestamp (version << 8 | cid) is at least min_ts, read from whichever residency the table is in
         (nothing is converted), asynchronously on `stream` (default: torch's current). out: a uint8 device buffer
         to write into (its whole records are the capacity) instead of a new one of `cap` records (default: the
         table's num_keys); result: two int64 words to write the counts into. Records past the capacity are counted,
         not written. min_ts only saves volume: the protocol has no global watermark, so whether the keys it leaves
-        out are current at the target is the caller's to know. Not for tables with RMWs."""
+        out are current at the target is the caller's to know. Not for tables with RMWs.
+        part_bits, part_mask (both or neither; None: the call above, unchanged): hkv_table_extract_parts_async --
+        only the buckets whose partition b & (2^part_bits - 1) has a non-zero byte in part_mask (uint8 device
+        tensor, 2^part_bits bytes; part_bits <= log2(num_bkts)) are read, and scanned_keys counts those alone."""
         dev = torch.device("cuda", self.device)
         E = self.sizes.entry
+        assert (part_bits is None) == (part_mask is None), "part_bits and part_mask go together"
         if out is None:
             out = torch.empty(max(int(self.num_keys if cap is None else cap), 1) * E, dtype=torch.uint8, device=dev)
             n_cap = int(self.num_keys if cap is None else cap)
@@ -522,6 +572,14 @@ class HermesKV:
         assert result.is_cuda and result.dtype == torch.int64 and result.is_contiguous() and result.numel() >= 2
         lo, hi = (0, self.cfg.num_bkts) if bkt_range is None else (int(bkt_range[0]), int(bkt_range[1]))
         s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        if part_mask is not None:
+            assert part_mask.is_cuda and part_mask.dtype == torch.uint8 and part_mask.is_contiguous()
+            assert part_mask.numel() >= 1 << int(part_bits)
+            check(_L.hkv_table_extract_parts_async(self.h, int(part_bits), ctypes.c_void_p(part_mask.data_ptr()), lo, hi,
+                                                   int(min_ts), ctypes.c_void_p(out.data_ptr()), n_cap,
+                                                   ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)),
+                  "hkv_table_extract_parts_async")
+            return Extract(out[:n_cap * E], result[:2], E)
         check(_L.hkv_table_extract_async(self.h, lo, hi, int(min_ts), ctypes.c_void_p(out.data_ptr()), n_cap,
                                          ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)),
               "hkv_table_extract_async")

@@ -69,6 +69,12 @@ class HkvInstallResult(ctypes.Structure):
                 ("missed", ctypes.c_uint64)]
 
 
+class HkvPartRow(ctypes.Structure):
+    """hkv_part_row (include/hermeskv.h, "Partitioned census and delta repair"): one partition's census"""
+    _fields_ = [("digest_sum", ctypes.c_uint64), ("digest_xor", ctypes.c_uint64), ("keys", ctypes.c_uint64),
+                ("not_valid", ctypes.c_uint64)]
+
+
 class Membership(ctypes.Structure):
     """spacetime_group_membership (8 bytes) by value. Declared as one 64-bit field: the SysV
     x86-64 ABI classifies both as a single INTEGER eightbyte, and libffi handles a scalar
@@ -109,6 +115,11 @@ _L.hkv_extract_result_bytes.restype = ctypes.c_uint32
 _L.hkv_install_result_bytes.restype = ctypes.c_uint32
 _L.hkv_table_extract_async.argtypes = [_P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]
 _L.hkv_table_install_async.argtypes = [_P, _P, ctypes.c_uint64, _P, _P]
+_L.hkv_part_row_bytes.restype = ctypes.c_uint32
+_L.hkv_table_census_parts_async.argtypes = [_P, ctypes.c_uint32, _P, _P]
+_L.hkv_part_rows_diff_async.argtypes = [_P, _P, ctypes.c_uint32, _P, _P, ctypes.c_int, _P]
+_L.hkv_table_extract_parts_async.argtypes = [_P, ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _P,
+                                             ctypes.c_uint64, _P, _P]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

@@ -807,6 +807,157 @@ def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buck
     return out
 
 
+def part_diff(rows_a, rows_b, mask: torch.Tensor | None = None):
+    """hkv_part_rows_diff_async on two partition censuses of the same part_bits (PartRows of
+    HermesKV.census_parts, or their [P, 4] int64 tensors): (mask, count), both on the device and with no host
+    read -- mask uint8[P], 1 where the two rows differ in any word; count int64[1], the non-zero bytes of mask.
+    Given `mask` (uint8[P], written in place), the result is or-ed into it: the union over several peers."""
+    a = getattr(rows_a, "tensor", rows_a)
+    b = getattr(rows_b, "tensor", rows_b)
+    assert a.shape == b.shape and a.dim() == 2 and a.shape[1] == 4, "two [P, 4] row tensors of one part_bits"
+    assert all(t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() for t in (a, b)) and a.device == b.device
+    P = a.shape[0]
+    part_bits = P.bit_length() - 1
+    assert P == 1 << part_bits
+    accumulate = mask is not None
+    if mask is None:
+        mask = torch.empty(P, dtype=torch.uint8, device=a.device)
+    assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == P
+    count = torch.empty(1, dtype=torch.int64, device=a.device)
+    with torch.cuda.device(a.device):
+        s = torch.cuda.current_stream(a.device).cuda_stream
+        check(raw().hkv_part_rows_diff_async(ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), part_bits,
+                                             ctypes.c_void_p(mask.data_ptr()), ctypes.c_void_p(count.data_ptr()),
+                                             int(accumulate), ctypes.c_void_p(s)), "hkv_part_rows_diff_async")
+    return mask, count
+
+
+def _selected_keys(rows_src: torch.Tensor, mask: torch.Tensor, count: torch.Tensor):
+    """(the source's live keys in the selected partitions -- the masked extract's record count, exact --, count)
+    in one host read"""
+    n = (rows_src[:, 2] * (mask != 0)).sum()
+    return tuple(int(v) for v in torch.stack([n, count[0]]).cpu().tolist())
+
+
+def _delta_verify(kvs: HermesKV, rows_src: torch.Tensor, part_bits: int) -> dict:
+    """the target's partition census again, against the source's rows: what still differs is reported"""
+    mask, count = part_diff(rows_src, kvs.census_parts(part_bits))
+    n = int(count.cpu()[0])
+    left = torch.nonzero(mask)[:64, 0].cpu().tolist() if n else []
+    return {"differing_after": n, "unresolved": [int(p) for p in left]}
+
+
+def _log2_buckets(num_bkts: int) -> int:
+    return int(num_bkts).bit_length() - 1
+
+
+def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chunk_buckets: int | None = None) -> dict:
+    """resync() that ships only the partitions that differ (include/hermeskv.h, "Partitioned census and delta
+    repair"), both tables in this process. In this order: HermesKV.census_parts of both tables at part_bits
+    (default: min(20, log2 of the smaller bucket count); at most log2 of either bucket count, so that every key of a
+    bucket lies in one partition whatever the geometry); part_diff; one host read of the source's key count in the
+    differing partitions, which sizes the record buffer exactly; the masked extract of `src` (in chunks of
+    chunk_buckets buckets, default the whole table, each chunk's count read on the host) and the install into `dst`;
+    the partition census of `dst` again, diffed against the source's rows.
+    Returns the summed install counts {raised, equal, older, missed} plus records and scanned_keys (of the selected
+    buckets only), partitions (2^part_bits), differing_before, differing_after and unresolved: the partitions that
+    still differ, at most 64 listed. A partition that still differs is reported, never hidden; two causes are
+    known: the target is newer in a key (its record counts as `older`), or the target lacks the key or shadows it
+    (its record counts as `missed`). Equal keys of a differing partition are shipped too and count as `equal`: the
+    install is timestamp-guarded. Every limit of resync() holds: sound only while `dst` takes no client operations
+    (INVs it receives meanwhile are safe); nothing is inserted; nobody is re-admitted to the membership; extract and
+    install refuse tables with RMWs."""
+    assert dst.sizes == src.sizes, "records of one entry size only"
+    if part_bits is None:
+        part_bits = min(20, _log2_buckets(min(src.cfg.num_bkts, dst.cfg.num_bkts)))
+    part_bits = int(part_bits)
+    dev = torch.device("cuda", src.device)
+    rows = src.census_parts(part_bits).tensor
+    mask, count = part_diff(rows, dst.census_parts(part_bits))
+    n, differing = _selected_keys(rows, mask, count)
+    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    records = scanned = 0
+    if n:
+        buf = torch.empty(n * src.sizes.entry, dtype=torch.uint8, device=dev)
+        res = torch.empty(2, dtype=torch.int64, device=dev)
+        for lo, hi in _bucket_chunks(src.cfg.num_bkts, chunk_buckets):
+            x = src.extract((lo, hi), out=buf, result=res, part_bits=part_bits, part_mask=mask)
+            h = x.host()
+            records, scanned = records + h["records"], scanned + h["scanned_keys"]
+            if h["records"]:
+                tot += dst.install(x, n=h["records"]).tensor
+        assert records == n, "the selected partitions' key counts are the masked extract's records"
+    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+    out.update(records=records, scanned_keys=scanned, partitions=1 << part_bits, differing_before=differing)
+    out.update(_delta_verify(dst, rows, part_bits))
+    return out
+
+
+def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part_bits: int | None,
+                       chunk_buckets: int | None) -> dict:
+    """delta_resync() across ranks. Collective: every rank of `group` calls it with the same arguments and its own
+    table (tables of one entry size; bucket counts may differ). part_bits None: min(20, log2 of the smallest bucket
+    count of the group), agreed by an all_reduce. The source rank broadcasts its partition rows; each stale rank
+    diffs them against its own; the masks are united over the ranks (all_reduce MAX of uint8, which gloo and NCCL /
+    RCCL both take); every rank reads the source's key count in the union -- the exact record count -- from the
+    rows it now holds. Per chunk the source extracts with the union mask and broadcasts the count, then the
+    records; only the ranks in stale_ranks install, and they alone take their partition census again and diff it
+    against the source's rows. Returns this rank's install counts (zeros where it did not install), records and
+    scanned_keys of the source, partitions, selected (partitions in the union), and this rank's differing_before,
+    differing_after and unresolved (0, 0 and [] where it is not stale). A stale rank's `equal` therefore covers
+    the keys of the partitions only another stale rank differed in. The conditions are delta_resync()'s: a stale
+    rank takes no client operations meanwhile, nothing is inserted, nobody is re-admitted to the membership here,
+    no tables with RMWs; a partition that still differs (the rank is newer in a key: `older`; it lacks or shadows
+    a key: `missed`) is reported in unresolved."""
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
+    stale = {int(r) for r in stale_ranks}
+    assert source_rank not in stale
+    dev = torch.device("cuda", kvs.device)
+    E = kvs.sizes.entry
+    geo = torch.tensor([kvs.cfg.num_bkts, _log2_buckets(kvs.cfg.num_bkts)], dtype=torch.int64, device=dev)
+    low = geo[1:].clone()
+    dist.broadcast(geo, src, group=group)
+    dist.all_reduce(low, op=dist.ReduceOp.MIN, group=group)
+    num_bkts, most_bits = int(geo[0].cpu()), int(low.cpu()[0])
+    part_bits = min(20, most_bits) if part_bits is None else int(part_bits)
+    assert part_bits <= most_bits, "part_bits above log2 of a rank's bucket count"
+    P = 1 << part_bits
+    mine = kvs.census_parts(part_bits).tensor
+    rows = mine.clone()
+    dist.broadcast(rows, src, group=group)
+    mask = torch.zeros(P, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if rank in stale:
+        mask, count = part_diff(rows, mine)
+    differing = count.clone()
+    dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=group)
+    n, selected = _selected_keys(rows, mask, (mask != 0).sum().reshape(1))
+    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    records = scanned = 0
+    if n:
+        buf = torch.empty(n * E, dtype=torch.uint8, device=dev)
+        res = torch.zeros(2, dtype=torch.int64, device=dev)
+        for lo, hi in _bucket_chunks(num_bkts, chunk_buckets):
+            if rank == source_rank:
+                kvs.extract((lo, hi), out=buf, result=res, part_bits=part_bits, part_mask=mask)
+            dist.broadcast(res, src, group=group)
+            m, sc = (int(v) for v in res.cpu().tolist())
+            assert records + m <= n, "more records than the selected partitions' keys"
+            records, scanned = records + m, scanned + sc
+            if not m:
+                continue
+            dist.broadcast(buf[:m * E], src, group=group)
+            if rank in stale:
+                tot += kvs.install(buf, n=m).tensor
+    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+    out.update(records=records, scanned_keys=scanned, partitions=P, selected=selected,
+               differing_before=int(differing.cpu()[0]))
+    out.update(_delta_verify(kvs, rows, part_bits) if rank in stale else {"differing_after": 0, "unresolved": []})
+    return out
+
+
 class LoopbackGroup:
     """N replicas driven phase by phase in one process; the collectives are tensor copies with
     exactly the layouts the RCCL driver produces (all-gather: row p = rank p's slab;

@@ -408,6 +408,61 @@ int hkv_table_extract_async(hkv_table *t, uint64_t bkt_lo, uint64_t bkt_hi, uint
 int hkv_table_install_async(hkv_table *t, const void *d_records, uint64_t n, hkv_install_result *d_result,
                             void *stream);
 
+/* Partitioned census and delta repair (ABI 10, functions only): anti-entropy by key range. The census says that
+ * two replicas differ, not where, so a repair ships every key. Here both sides take the census per partition of
+ * the key space, the rows are compared, and only the partitions that differ are extracted and installed.
+ *
+ * Partition. For part_bits b and P = 2^b, key k lies in partition k & (P - 1). A key's bucket is
+ * k & 0xFFFFFFFFFFFF & (num_bkts - 1), so with P <= num_bkts -- the rule part_bits <= log2(num_bkts), which
+ * every call below enforces -- a bucket's number has the same low b bits as every key in it: all keys of a bucket
+ * lie in one partition, on any table with at least P buckets, whatever its bucket count, log order or residency.
+ * Two replicas compare rows taken with the same part_bits; their geometries need not agree.
+ *
+ * hkv_table_census_parts_async. rows[p], p < P, holds the census's digest_sum, digest_xor, keys and offenders
+ * (here: not_valid) restricted to the live keys of partition p; d_rows is P rows of device memory, 16-byte
+ * aligned, overwritten, not accumulated. Over p the rows fold to the census: digest_sum by addition modulo 2^64,
+ * digest_xor by xor, keys and not_valid by addition (to keys and offenders); part_bits 0 gives one row equal to
+ * those four census fields. Liveness, residency and ordering are the census's: a slot is live when it is in use
+ * and log_head - offset < log_cap; the table is read as it is (an INLINE table's inline keys from their lines,
+ * never from their stale log copies); nothing is converted and conversions / inline_launches do not move; the
+ * call is asynchronous on `stream`, ordered after the table's last stream, takes one caller at a time, and stops
+ * a live serving kernel first. Every field is a sum or an xor, so equal tables give equal bytes, and a second
+ * call into the same buffer gives the same bytes. Tables with RMWs are accepted, as by the census.
+ *
+ * hkv_part_rows_diff_async. d_mask[p] = 1 where rows a and b differ in any of the four words, else 0; with
+ * accumulate != 0 the byte that is there is or-ed with that instead (the union over several peers). *d_count =
+ * the non-zero bytes of d_mask afterwards. No table is involved: it is ordered by `stream` alone.
+ *
+ * hkv_table_extract_parts_async. hkv_table_extract_async restricted to the buckets of [bkt_lo, bkt_hi) whose
+ * partition b & (P - 1) has a non-zero byte in d_part_mask (P bytes; any non-zero value selects). An unselected
+ * bucket is not read: scanned_keys counts the live slots of the selected buckets of the range only. records,
+ * record_cap and "nothing at or past min(records, record_cap) * E is touched" are the extract's. With min_ts 0
+ * and the whole bucket range, records is the sum of rows[p].keys over the selected partitions.
+ *
+ * Refusals, with a negative code and a message in hkv_last_error() that names the call, before anything is
+ * launched: a NULL table (or rows, mask, count); part_bits > log2(num_bkts); rows not 16-byte aligned; for the
+ * masked extract everything hkv_table_extract_async refuses (RMW tables among it) and a NULL mask.
+ *
+ * A delta repair (hermes_amd.replica_group.delta_resync) is: both partition censuses, the diff, the masked
+ * extract of the source, the install into the target, and the target's partition census again. Shipping a whole
+ * differing partition is harmless for its keys that were equal, the install being timestamp-guarded. Every limit
+ * of a repair holds: the target takes no client operations meanwhile, nothing is inserted, nobody is re-admitted
+ * to the membership, and extract and install refuse RMW tables. A partition can still differ afterwards, and is
+ * then reported, not hidden; two causes are known: the target is newer in a key (that record counts as `older`),
+ * or the target lacks the key or shadows it behind another (that record counts as `missed`). */
+typedef struct hkv_part_row {
+    uint64_t digest_sum, digest_xor;   /* the census's, over the partition's live keys */
+    uint64_t keys;                     /* live keys of the partition */
+    uint64_t not_valid;                /* of them, not VALID (adds up to hkv_census.offenders) */
+} hkv_part_row;
+uint32_t hkv_part_row_bytes(void);   /* sizeof(hkv_part_row) = 32, for bindings */
+int hkv_table_census_parts_async(hkv_table *t, uint32_t part_bits, hkv_part_row *d_rows, void *stream);
+int hkv_part_rows_diff_async(const hkv_part_row *d_a, const hkv_part_row *d_b, uint32_t part_bits,
+                             uint8_t *d_mask, uint64_t *d_count, int accumulate, void *stream);
+int hkv_table_extract_parts_async(hkv_table *t, uint32_t part_bits, const uint8_t *d_part_mask,
+                                  uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, void *d_records,
+                                  uint64_t record_cap, hkv_extract_result *d_result, void *stream);
+
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
 hkv_table *hkv_default_table(void);
