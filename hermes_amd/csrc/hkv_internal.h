@@ -211,8 +211,39 @@ int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t 
                          hipStream_t s);
 // Install: n records, no key twice, applied as an INV and (source VALID) a VAL each to the entries of `log`, or,
 // with `line` non-NULL, to the lines for the inline keys; result[0..3] (raised, equal, older, missed) zeroed first.
+// missed_flag (may be NULL: the install itself): one byte per record, 1 when the record was missed, else 0;
+// 16-byte aligned and n rounded up to 64 bytes long (a wave stores its 16 records' bytes at once, zero past n).
 int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,
-                         uint64_t n, unsigned long long *result, hipStream_t s);
+                         uint64_t n, unsigned long long *result, hipStream_t s, uint8_t *missed_flag = nullptr);
+// The upsert's inserts (hermeskv.h "Upsert", step 2) into index and log, after an install with missed_flag and the
+// host's read of its missed count m (1 <= m <= n <= 2^31 - 1): the scan of the flags into ranks, the missed
+// records' (bucket, rank) pairs, their stable sort by bucket, the per-bucket replay of mica_insert_one, and the
+// log entries. g.log_head is not read: h0, k, hw are plan_log's for m inserts from the table's head (h0 a multiple
+// of 16). Scratch, all device memory: flags [n], ranks [n], scan_tmp; keys_a/b, vals_a/b, rec_of [m] 32-bit each,
+// key_of [m] 64-bit, sort_tmp. counts[0] += replaced, counts[1] += evictions (the caller zeroes them); evictions:
+// the table's counter. phase_events (may be NULL): four events, recorded after the scan and the pairs, the sort,
+// the replay and the log writes.
+struct UpsertLaunch {
+    Geometry g;
+    uint8_t *index, *log;
+    const uint8_t *records;
+    uint64_t n, m;
+    const uint8_t *flags;
+    uint32_t *ranks;
+    void *scan_tmp;
+    size_t scan_tmp_bytes;
+    uint32_t *keys_a, *keys_b, *vals_a, *vals_b, *rec_of;
+    uint64_t *key_of;
+    void *sort_tmp;
+    size_t sort_tmp_bytes;
+    unsigned long long *evictions, *counts;
+    uint64_t h0, k, hw;
+    int32_t key_bits;
+    uint8_t val_len_byte;
+    hipEvent_t *phase_events;
+};
+size_t scan_temp_bytes(uint64_t n);
+int launch_upsert_inserts(const UpsertLaunch &u, hipStream_t s);
 // whether launch_batch runs this launch on kernels that know the inline residency (bl.line aside)
 bool batch_inline_capable(const BatchLaunch &bl);
 

@@ -84,10 +84,14 @@ __device__ __forceinline__ uint64_t plan_off(const LogPlan &L, uint64_t p)
     return p < L.k ? L.h0 + p * L.e : L.hw + (p - L.k) * L.e;
 }
 
-// one owner lane per bucket replays mica_insert_one (mica.c:78-146) for that bucket's inserts
+// one owner lane per bucket replays mica_insert_one (mica.c:78-146) for that bucket's inserts, starting from the
+// bucket as it is in memory. Insert p's tag is that of key[p], its offset plan_off(L, p). The sort is stable, so a
+// bucket's inserts arrive in the order of p. COUNT (the upsert; a populate's instance is the code it was): also
+// counts[0] += inserts that took an in-use slot by tag match, counts[1] += evictions.
+template <bool COUNT>
 __global__ void k_pop_buckets(const uint32_t *__restrict__ sk, const uint32_t *__restrict__ sp,
-                              const uint64_t *__restrict__ second, uint8_t *index, int64_t n,
-                              LogPlan L, unsigned long long *evictions)
+                              const uint64_t *__restrict__ key, uint8_t *index, int64_t n,
+                              LogPlan L, unsigned long long *evictions, unsigned long long *counts)
 {
     int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
@@ -97,18 +101,23 @@ __global__ void k_pop_buckets(const uint32_t *__restrict__ sk, const uint32_t *_
     uint64_t s[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) s[j] = slots[j];
-    unsigned long long ev = 0;
+    unsigned long long ev = 0, rep = 0;
     for (int64_t r = q; r < n && sk[r] == bkt; ++r) {
         uint32_t p = sp[r];
-        uint32_t tag = (uint32_t)(second[p] >> 48);
+        uint32_t tag = (uint32_t)(key[p] >> 48);
         int use = -1;
+        bool taken = false;   // the chosen slot was in use
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-            if (slot_tag(s[j]) == tag || !slot_in_use(s[j])) use = j;
+            if (slot_tag(s[j]) == tag || !slot_in_use(s[j])) {
+                use = j;
+                if (COUNT) taken = slot_in_use(s[j]);
+            }
         if (use < 0) {
             use = (int)(tag & 7u);
             ++ev;
         }
+        if (COUNT) rep += taken;
         uint64_t v = 1u | ((uint64_t)tag << 1) | (plan_off(L, p) << 24);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -117,6 +126,10 @@ __global__ void k_pop_buckets(const uint32_t *__restrict__ sk, const uint32_t *_
 #pragma unroll
     for (int j = 0; j < 8; ++j) slots[j] = s[j];
     if (ev) atomicAdd(evictions, ev);
+    if (COUNT) {
+        if (rep) atomicAdd(&counts[0], rep);
+        if (ev) atomicAdd(&counts[1], ev);
+    }
 }
 
 // entry image of spacetime_populate_fixed_len (spacetime.c:32-68); meta fields the reference
@@ -188,8 +201,8 @@ int launch_populate(const PopulateLaunch &pl, hipStream_t s)
     if (sort_pairs(pl.sort_tmp, pl.sort_tmp_bytes, pl.keys_a, pl.keys_b, pl.vals_a, pl.vals_b, n, pl.key_bits, s))
         return -2;
     LogPlan L{pl.h0, pl.k, pl.hw, pl.entry_size};
-    hipLaunchKernelGGL(k_pop_buckets, dim3(grid), dim3(256), 0, s, pl.keys_b, pl.vals_b, pl.second, pl.index, n, L,
-                       pl.evictions);
+    hipLaunchKernelGGL(k_pop_buckets<false>, dim3(grid), dim3(256), 0, s, pl.keys_b, pl.vals_b, pl.second, pl.index, n,
+                       L, pl.evictions, (unsigned long long *)nullptr);
     if (hipGetLastError() != hipSuccess) return -3;
     // later inserts overwrite earlier ones when the log wraps: write in chunks no longer than one
     // physical lap, in insertion order
@@ -827,13 +840,47 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_extract(const uint8_t *_
 // back only the 16-B chunks of bytes 16..63 that changed; the lock byte, ack_bv, op buffer index and last-local-
 // write timestamp go back as they were read. A 320-B entry's other 256 value bytes move 64 consecutive bytes
 // per group and instruction. No key occurs twice, so no two groups share an entry.
-template <bool IL, bool BIG>
+// FLAGS (the upsert's first step, hermeskv.h "Upsert"): also missed_flag[i] = 1 when record i was missed, else 0 --
+// a template parameter, so that the install's own instances are the code they were.
+enum : uint32_t { kMissed = 0, kOlder = 1, kEqual = 2, kRaised = 3 };
+
+// Lane 1's decision: ln = the entry's bytes 16..31, r = the record's. hermes_exec_inv of the record's INV, then
+// hermes_exec_val when the record is VALID, on a table without RMWs; nl = the bytes afterwards. The upsert's log
+// writer applies the same to the image it inserts.
+__device__ __forceinline__ uint32_t install_decide(const uint4 &ln, const uint4 &r, uint32_t kvs_value, uint4 &nl)
+{
+    uint32_t d;
+    uint32_t w4 = ln.x, w5 = ln.y, ver = ln.z;
+    const uint32_t r_state = (r.x >> 16) & 0xFFu, r_cid = r.y >> 24, r_ver = r.z;
+    const uint64_t its = ((uint64_t)r_ver << 8) | r_cid, cur = ((uint64_t)ver << 8) | (w5 >> 24);
+    if (its > cur) {   // hermes_exec_inv, the newer INV
+        d = kRaised;
+        const uint32_t st = (w4 >> 16) & 0xFFu;
+        const uint32_t ns = st == kValid ? kInvalid : (st == kWrite || st == kReplay) ? kInvalidWrite : st;
+        w4 = (w4 & 0xFF0000FFu) | ((kvs_value & 0xFFu) << 8) | (ns << 16);        // val_len, state
+        w5 = (w5 & 0x00FFFF00u) | ((r_cid & 0x7Fu) << 1) | (r_cid << 24);         // RMW flag 0, last writer, ts cid
+        ver = r_ver;
+    } else if (its == cur) {
+        d = kEqual;
+        w5 = (w5 & ~0xFEu) | ((r_cid & 0x7Fu) << 1);                              // last writer
+    } else {
+        d = kOlder;
+    }
+    if (d >= kEqual && r_state == kValid) w4 = (w4 & 0xFF00FFFFu) | ((uint32_t)kValid << 16);   // hermes_exec_val
+    nl.x = w4;
+    nl.y = w5;
+    nl.z = ver;
+    return d;
+}
+
+template <bool IL, bool BIG, bool FLAGS>
 __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *__restrict__ index, uint8_t *log,
                                                                 uint8_t *line, const uint4 *__restrict__ records,
                                                                 uint64_t n, uint64_t bkt_mask, uint64_t log_mask,
                                                                 uint64_t log_head, uint64_t log_cap,
                                                                 uint32_t kvs_value, uint32_t chunks,
-                                                                unsigned long long *result)
+                                                                unsigned long long *result,
+                                                                uint8_t *__restrict__ missed_flag)
 {
     Geometry g{};   // (the fields the probe reads)
     g.bkt_mask = bkt_mask, g.log_mask = log_mask, g.log_head = log_head, g.log_cap = log_cap;
@@ -864,31 +911,9 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
         uint4 ln = make_uint4(0u, 0u, 0u, 0u);
         if (ok) ln = il ? ev : home[q];
         const bool hit = ok && __shfl(u64_of(ln.z, ln.w), 0, 4) == key;
-        enum : uint32_t { kMissed = 0, kOlder = 1, kEqual = 2, kRaised = 3 };
         uint32_t d = kMissed;
         uint4 nl = ln;
-        if (q == 1 && hit) {   // ln: entry bytes 16..31; r: the record's
-            uint32_t w4 = ln.x, w5 = ln.y, ver = ln.z;
-            const uint32_t r_state = (r.x >> 16) & 0xFFu, r_cid = r.y >> 24, r_ver = r.z;
-            const uint64_t its = ((uint64_t)r_ver << 8) | r_cid, cur = ((uint64_t)ver << 8) | (w5 >> 24);
-            if (its > cur) {   // hermes_exec_inv, the newer INV
-                d = kRaised;
-                const uint32_t st = (w4 >> 16) & 0xFFu;
-                const uint32_t ns = st == kValid ? kInvalid : (st == kWrite || st == kReplay) ? kInvalidWrite : st;
-                w4 = (w4 & 0xFF0000FFu) | ((kvs_value & 0xFFu) << 8) | (ns << 16);        // val_len, state
-                w5 = (w5 & 0x00FFFF00u) | ((r_cid & 0x7Fu) << 1) | (r_cid << 24);         // RMW flag 0, last writer, ts cid
-                ver = r_ver;
-            } else if (its == cur) {
-                d = kEqual;
-                w5 = (w5 & ~0xFEu) | ((r_cid & 0x7Fu) << 1);                              // last writer
-            } else {
-                d = kOlder;
-            }
-            if (d >= kEqual && r_state == kValid) w4 = (w4 & 0xFF00FFFFu) | ((uint32_t)kValid << 16);   // hermes_exec_val
-            nl.x = w4;
-            nl.y = w5;
-            nl.z = ver;
-        }
+        if (q == 1 && hit) d = install_decide(ln, r, kvs_value, nl);   // ln: entry bytes 16..31; r: the record's
         d = __shfl(d, 1, 4);
         if (d == kRaised) {   // the value: bytes 33..63 here (byte 32 is the entry's own), the rest below
             if (q == 2) nl = make_uint4((ln.x & 0xFFu) | (r.x & ~0xFFu), r.y, r.z, r.w);
@@ -909,6 +934,22 @@ __global__ __launch_bounds__(kCensusBlock) void k_table_install(const uint8_t *_
             }
         }
         const bool mine = q == 1 && live;
+        if (FLAGS) {
+            // a wave's 16 records are 16 consecutive flag bytes: one 16-B store by its first lane instead of 16
+            // byte stores (measured level with them). The store may run up to 63 bytes past n, inside
+            // the flags' allocation (the caller rounds it up), with zero bytes.
+            const unsigned long long bm = __ballot(mine && d == kMissed);   // bit 4g + 1: the wave's g-th record
+            if ((threadIdx.x & 63) == 0) {
+                uint32_t w[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const uint32_t nib = (uint32_t)(bm >> (16 * k + 1));   // bits 0, 4, 8, 12: four records
+                    w[k] = (nib & 1u) | ((nib >> 4 & 1u) << 8) | ((nib >> 8 & 1u) << 16) | ((nib >> 12 & 1u) << 24);
+                }
+                uint8_t *dst = missed_flag + i0 + (threadIdx.x >> 6) * 16;   // (i0 is a multiple of 64)
+                *reinterpret_cast<uint4 *>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+            }
+        }
         cnt[0] += mine && d == kRaised;
         cnt[1] += mine && d == kEqual;
         cnt[2] += mine && d == kOlder;
@@ -940,7 +981,7 @@ int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t 
 }
 
 int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,
-                         uint64_t n, unsigned long long *result, hipStream_t s)
+                         uint64_t n, unsigned long long *result, hipStream_t s, uint8_t *missed_flag)
 {
     const uint32_t chunks = g.entry_size / 64;
     const bool big = chunks > 1;
@@ -952,11 +993,143 @@ int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, 
     // 8 blocks per CU, what the CUs hold at once at the instances' 8 waves per SIMD: no occupancy query
     const dim3 grid = persistent_grid(nullptr, n, kCensusBktsPerBlock, device, 8);
     with_instance(line != nullptr, big, [&](auto il, auto bg) {
-        hipLaunchKernelGGL((k_table_install<decltype(il)::value, decltype(bg)::value>), grid, dim3(kCensusBlock), 0, s,
-                           index, log, line, reinterpret_cast<const uint4 *>(records), n, g.bkt_mask, g.log_mask,
-                           g.log_head, g.log_cap, g.kvs_value, chunks, result);
+        const auto launch = [&](auto k) {
+            hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line,
+                               reinterpret_cast<const uint4 *>(records), n, g.bkt_mask, g.log_mask, g.log_head,
+                               g.log_cap, g.kvs_value, chunks, result, missed_flag);
+        };
+        if (missed_flag) launch(k_table_install<decltype(il)::value, decltype(bg)::value, true>);
+        else launch(k_table_install<decltype(il)::value, decltype(bg)::value, false>);
     });
     return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// ------------------------------------------------------------------ upsert: the inserts
+// hermeskv.h "Upsert", step 2, after the install with FLAGS has marked the missed records and the host has read
+// their number m. Rank: an exclusive scan of the flags gives each missed record its place among them in record
+// order -- its log rank, which plan_off turns into the offset mica_insert_one would hand out (an atomic append
+// would make the log order a matter of scheduling). Pairs: rank r's bucket and r itself, with key[r] and the
+// record's index beside them; the stable sort by bucket and the populate's k_pop_buckets then replay each bucket's
+// inserts in rank order, which is record order. Log: one group of four lanes per rank reads its record once, forms
+// the final entry in registers and writes it as whole 64-byte runs, 16 B per lane.
+namespace {
+struct FlagToRank {
+    __device__ uint32_t operator()(uint8_t f) const { return f ? 1u : 0u; }
+};
+}  // namespace
+
+size_t scan_temp_bytes(uint64_t n)
+{
+    size_t bytes = 0;
+    rocprim::exclusive_scan(nullptr, bytes, rocprim::make_transform_iterator((const uint8_t *)nullptr, FlagToRank{}),
+                            (uint32_t *)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>());
+    return bytes;
+}
+
+__global__ __launch_bounds__(kCensusBlock) void k_ups_pairs(const uint8_t *__restrict__ flags,
+                                                            const uint32_t *__restrict__ ranks,
+                                                            const uint8_t *__restrict__ records, uint64_t n,
+                                                            uint32_t entry_size, uint64_t bkt_mask,
+                                                            uint32_t *__restrict__ bkt_keys, uint32_t *__restrict__ pos,
+                                                            uint64_t *__restrict__ key_of,
+                                                            uint32_t *__restrict__ rec_of)
+{
+    const uint64_t step = (uint64_t)gridDim.x * kCensusBlock;
+    for (uint64_t i = (uint64_t)blockIdx.x * kCensusBlock + threadIdx.x; i < n; i += step) {
+        if (!flags[i]) continue;
+        const uint32_t r = ranks[i];   // (below m, the flags' total, which sized the arrays)
+        const uint64_t key = *reinterpret_cast<const uint64_t *>(records + i * entry_size + 8);
+        bkt_keys[r] = (uint32_t)((key & 0xFFFFFFFFu) & bkt_mask);   // mica_insert_one: 32-bit bkt field
+        pos[r] = r;
+        key_of[r] = key;
+        rec_of[r] = (uint32_t)i;
+    }
+}
+
+// The entry an inserted record leaves (hermeskv.h "Upsert", step 2): the populate image (k_pop_log) with bytes
+// 0..7 zero, the record's key and value, then the record's INV and VAL applied to it as the install applies them.
+template <bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_ups_log(const uint4 *__restrict__ records,
+                                                          const uint32_t *__restrict__ rec_of, uint8_t *log,
+                                                          uint64_t p_begin, uint64_t p_end, LogPlan L,
+                                                          uint64_t log_mask, uint32_t kvs_value, uint32_t val_len_byte, uint32_t chunks)
+{
+    const uint64_t E4 = BIG ? 4ull * chunks : 4ull;   // 16-B chunks of a record
+    const int q = threadIdx.x & 3;
+    for (uint64_t p0 = p_begin + (uint64_t)blockIdx.x * kCensusBktsPerBlock; p0 < p_end;
+         p0 += (uint64_t)gridDim.x * kCensusBktsPerBlock) {   // (block-uniform)
+        const uint64_t p = p0 + (threadIdx.x >> 2);
+        if (p >= p_end) continue;   // (the four lanes of a group share p; nothing below crosses lanes)
+        const uint64_t i = rec_of[p];
+        const uint4 r = records[i * E4 + q];
+        uint4 img = r;   // q == 3: value bytes
+        if (q == 0) img = make_uint4(0u, 0u, r.z, r.w);   // no key_first; the key
+        if (q == 1) {
+            // bytes 16..23: opcode PUT, val_len, state VALID, ack_bv 0, lwid 127, obi 255, lock 0, cid 255; 24..31: 0
+            const uint32_t w4 = (uint32_t)kOpPut | (val_len_byte << 8) | ((uint32_t)kValid << 16);
+            const uint32_t w5 = (uint32_t)(kLwidEmpty << 1) | ((uint32_t)kObiEmpty << 8) | ((uint32_t)kCidEmpty << 24);
+            const uint4 ln = make_uint4(w4, w5, 0u, 0u);
+            img = ln;
+            (void)install_decide(ln, r, kvs_value, img);
+        }
+        if (q == 2) img.x = r.x & ~0xFFu;   // byte 32 is the entry's own (last-local-write version), the value from 33
+        uint4 *dst = reinterpret_cast<uint4 *>(log + (plan_off(L, p) & log_mask));
+        dst[q] = img;
+        if (BIG)
+            for (uint32_t k = 1; k < chunks; ++k) dst[4 * k + q] = records[i * E4 + 4 * k + q];
+    }
+}
+
+int launch_upsert_inserts(const UpsertLaunch &u, hipStream_t s)
+{
+    const Geometry &g = u.g;
+    const uint32_t chunks = g.entry_size / 64;
+    if (g.entry_size % 64 || !u.m || u.m > u.n || u.n > 0x7FFFFFFFull || (u.h0 & 15)) return -1;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) device = -1;
+    const auto mark = [&](int k) {
+        if (u.phase_events) (void)hipEventRecord(u.phase_events[k], s);
+    };
+    size_t scan_bytes = u.scan_tmp_bytes;
+    if (rocprim::exclusive_scan(u.scan_tmp, scan_bytes,
+                                rocprim::make_transform_iterator(u.flags, FlagToRank{}), u.ranks, 0u, (size_t)u.n,
+                                rocprim::plus<uint32_t>(), s) != hipSuccess)
+        return -2;
+    hipLaunchKernelGGL(k_ups_pairs, persistent_grid(nullptr, u.n, kCensusBlock, device, 8), dim3(kCensusBlock), 0, s,
+                       u.flags, u.ranks, u.records, u.n, g.entry_size, g.bkt_mask, u.keys_a, u.vals_a, u.key_of,
+                       u.rec_of);
+    if (hipGetLastError() != hipSuccess) return -3;
+    mark(0);
+    if (sort_pairs(u.sort_tmp, u.sort_tmp_bytes, u.keys_a, u.keys_b, u.vals_a, u.vals_b, (int64_t)u.m, u.key_bits, s))
+        return -4;
+    mark(1);
+    LogPlan L{u.h0, u.k, u.hw, g.entry_size};
+    hipLaunchKernelGGL(k_pop_buckets<true>, dim3((unsigned)((u.m + 255) / 256)), dim3(256), 0, s, u.keys_b, u.vals_b,
+                       u.key_of, u.index, (int64_t)u.m, L, u.evictions, u.counts);
+    if (hipGetLastError() != hipSuccess) return -5;
+    mark(2);
+    // as launch_populate: no launch overlaps itself across the single wrap or across one lap of the log, and the
+    // launches run in rank order, so a later insert overwrites an earlier one where the reference's would
+    uint64_t chunk = g.log_cap / g.entry_size;
+    if (chunk < 1) chunk = 1;
+    const uint64_t wrap_at = u.k < u.m ? u.k : u.m;
+    const uint64_t runs[2][2] = {{0, wrap_at}, {wrap_at, u.m}};
+    for (const auto &r : runs) {
+        for (uint64_t b = r[0]; b < r[1]; b += chunk) {
+            const uint64_t e = b + chunk < r[1] ? b + chunk : r[1];
+            const dim3 grid = persistent_grid(nullptr, e - b, kCensusBktsPerBlock, device, 8);
+            const auto recs = reinterpret_cast<const uint4 *>(u.records);
+            const auto launch = [&](auto k) {
+                hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, recs, u.rec_of, u.log, b, e, L, g.log_mask,
+                                   g.kvs_value, (uint32_t)u.val_len_byte, chunks);
+            };
+            if (chunks > 1) launch(k_ups_log<true>);
+            else launch(k_ups_log<false>);
+            if (hipGetLastError() != hipSuccess) return -6;
+        }
+    }
+    mark(3);
+    return 0;
 }
 
 }  // namespace hkv

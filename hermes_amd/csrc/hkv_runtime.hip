@@ -153,6 +153,15 @@ struct hkv_table {
         int64_t n = 0;
         const uint8_t *elems = nullptr;
     } pre;
+    // hkv_table_upsert's scratch (ensure_upsert_scratch), kept until hkv_table_destroy: per record (ranks, flags,
+    // scan storage) and per insert (keys, pairs, record indices, sort storage), each grown geometrically like
+    // d_batch; six result words (raised, equal, older, missed, replaced, evictions)
+    uint8_t *d_ups_rec = nullptr, *d_ups_ins = nullptr;
+    uint64_t ups_rec_cap = 0, ups_ins_cap = 0;
+    size_t ups_scan_bytes = 0, ups_sort_bytes = 0;
+    unsigned long long *d_ups_res = nullptr;
+    hipEvent_t ups_ev[7] = {};          // HKV_UPSERT_PHASES: the last upsert's phases (hkv_debug_upsert_phases)
+    float ups_ms[5] = {0, 0, 0, 0, 0};
     unsigned int *d_error_flags = nullptr;
     int32_t *d_ns_idx = nullptr;
     int32_t ns_cap = 0;
@@ -468,6 +477,11 @@ int hkv_table_destroy(hkv_table *t)
     hipFree(t->d_evictions);
     hipFree(t->d_batch);
     hipFree(t->d_fw);
+    hipFree(t->d_ups_rec);
+    hipFree(t->d_ups_ins);
+    hipFree(t->d_ups_res);
+    for (hipEvent_t e : t->ups_ev)
+        if (e) hipEventDestroy(e);
     hipFree(t->d_error_flags);
     hipFree(t->d_ns_idx);
     for (HostSet &hs : t->sets) {
@@ -1020,6 +1034,156 @@ int hkv_table_extract_parts_async(hkv_table *t, uint32_t part_bits, const uint8_
                                     reinterpret_cast<unsigned long long *>(d_result), d_part_mask, part_bits,
                                     t->cfg.device, s);
     });
+}
+
+// Upsert (hermeskv.h "Upsert"): the install with a missed flag per record through table_pass (the table as it is,
+// nothing converted), the one host read that decides the rest (the install's counts), and, when anything was
+// missed, the table to LOG as before a populate and the inserts into index and log (launch_upsert_inserts). The
+// per-line F/X/Y/T words are not touched.
+static_assert(sizeof(hkv_upsert_result) == 64, "hkv_upsert_result is eight 64-bit words");
+uint32_t hkv_upsert_result_bytes(void) { return (uint32_t)sizeof(hkv_upsert_result); }
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+static int upsert_key_bits(const hkv_table *t)
+{
+    const int b = bit_width(t->cfg.num_bkts - 1);
+    return b ? b : 1;
+}
+
+// scratch for n records of which m are inserted; either part grows geometrically and is kept (a chunked resync
+// allocates once)
+static int ensure_upsert_scratch(hkv_table *t, uint64_t n, uint64_t m)
+{
+    if (!t->d_ups_res) HIP_TRY(hipMalloc(&t->d_ups_res, 8 * sizeof(unsigned long long)));
+    if (n > t->ups_rec_cap) {
+        const uint64_t cap = n + n / 4 + 1024;
+        hipFree(t->d_ups_rec);
+        t->d_ups_rec = nullptr;
+        t->ups_rec_cap = 0;
+        const size_t scan = scan_temp_bytes(cap);
+        HIP_TRY(hipMalloc(&t->d_ups_rec, up256(4 * cap) + up256(cap) + up256(scan)));
+        t->ups_rec_cap = cap;
+        t->ups_scan_bytes = scan;
+    }
+    if (m > t->ups_ins_cap) {
+        const uint64_t cap = m + m / 4 + 1024;
+        hipFree(t->d_ups_ins);
+        t->d_ups_ins = nullptr;
+        t->ups_ins_cap = 0;
+        const size_t sort = sort_temp_bytes((int64_t)cap, upsert_key_bits(t));
+        HIP_TRY(hipMalloc(&t->d_ups_ins, up256(8 * cap) + 5 * up256(4 * cap) + up256(sort)));
+        t->ups_ins_cap = cap;
+        t->ups_sort_bytes = sort;
+    }
+    return 0;
+}
+
+static const bool g_ups_phases = getenv("HKV_UPSERT_PHASES") != nullptr;
+
+int hkv_table_upsert(hkv_table *t, const void *d_records, uint64_t n, hkv_upsert_result *host_result, void *stream)
+{
+    if (!t || !d_records || !host_result) return fail(-1, "upsert: null argument");
+    if (t->cfg.rmw_enabled) return fail(-2, "upsert: the table has RMWs enabled (a record carries no RMW flag)");
+    if ((uintptr_t)d_records & 15) return fail(-1, "upsert: d_records must be 16-byte aligned");
+    if (n > 0x7FFFFFFFull) return fail(-1, "upsert: at most 2^31-1 records (32-bit record indices)");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(t->cfg.device));
+    {
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (int rc = ensure_upsert_scratch(t, n, 0)) return rc;
+        if (g_ups_phases)
+            for (hipEvent_t &e : t->ups_ev)
+                if (!e) HIP_TRY(hipEventCreate(&e));
+        for (float &ms : t->ups_ms) ms = 0.f;
+    }
+    uint32_t *ranks = reinterpret_cast<uint32_t *>(t->d_ups_rec);
+    uint8_t *flags = t->d_ups_rec + up256(4 * t->ups_rec_cap);
+    void *scan_tmp = flags + up256(t->ups_rec_cap);
+    unsigned long long *res = t->d_ups_res;
+    const uint8_t *records = static_cast<const uint8_t *>(d_records);
+    hipEvent_t *ev = g_ups_phases ? t->ups_ev : nullptr;
+    PASS_DETAIL(d, " %llu records", (unsigned long long)n);
+    if (int rc = table_pass(t, stream, "upsert", d, [&](uint8_t *line, hipStream_t ps) {
+            if (ev) (void)hipEventRecord(ev[0], ps);
+            const int lrc = launch_table_install(t->geo, t->d_index, t->d_log, line, records, n, res, ps, flags);
+            if (ev) (void)hipEventRecord(ev[1], ps);
+            return lrc;
+        }))
+        return rc;
+    // the one host read that decides the rest: the install's counts, `missed` among them
+    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(h, res, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const uint64_t m = h[3];
+    if (m) {
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (int rc = layout_export(t)) return rc;   // inserts go into index and log, as a populate's
+        if (int rc = ensure_upsert_scratch(t, n, m)) return rc;
+        HIP_TRY(hipMemsetAsync(res + 4, 0, 2 * sizeof(unsigned long long), s));
+        const uint64_t cap = t->ups_ins_cap;
+        UpsertLaunch u;
+        memset(&u, 0, sizeof u);
+        u.g = t->geo;
+        u.index = t->d_index;
+        u.log = t->d_log;
+        u.records = records;
+        u.n = n;
+        u.m = m;
+        u.flags = flags;
+        u.ranks = ranks;
+        u.scan_tmp = scan_tmp;
+        u.scan_tmp_bytes = t->ups_scan_bytes;
+        uint8_t *p = t->d_ups_ins;
+        u.key_of = reinterpret_cast<uint64_t *>(p);
+        p += up256(8 * cap);
+        uint32_t **words[5] = {&u.keys_a, &u.keys_b, &u.vals_a, &u.vals_b, &u.rec_of};
+        for (uint32_t **w : words) {
+            *w = reinterpret_cast<uint32_t *>(p);
+            p += up256(4 * cap);
+        }
+        u.sort_tmp = p;
+        u.sort_tmp_bytes = t->ups_sort_bytes;
+        u.evictions = t->d_evictions;
+        u.counts = res + 4;
+        u.key_bits = upsert_key_bits(t);
+        u.val_len_byte = (uint8_t)(t->geo.kvs_value >> t->geo.shift);   // spacetime.c:45 with KVS_VALUE_SIZE
+        u.phase_events = ev ? ev + 3 : nullptr;
+        uint64_t final_head;
+        u.h0 = t->geo.log_head;
+        plan_log(t->geo.log_head, t->geo.log_cap, t->geo.entry_size, t->geo.kvs_value, m, u.k, u.hw, final_head);
+        if (ev) (void)hipEventRecord(ev[2], s);
+        const int rc = launch_upsert_inserts(u, s);
+        const hipError_t se = hipStreamSynchronize(s);
+        if (rc) return fail(rc, "upsert: insert launch failed (%d): %s", rc, hipGetErrorString(hipGetLastError()));
+        if (se != hipSuccess) return fail(-5, "upsert: %s", hipGetErrorString(se));
+        HIP_TRY(hipMemcpy(h + 4, res + 4, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        t->geo.log_head = final_head;
+        t->inserted += (int64_t)m;
+        t->last_stream = s;
+        TRACE("upsert: %llu inserted, head %llu", (unsigned long long)m, (unsigned long long)final_head);
+    }
+    if (ev) {
+        (void)hipEventElapsedTime(&t->ups_ms[0], ev[0], ev[1]);
+        if (m)
+            for (int k = 1; k < 5; ++k) (void)hipEventElapsedTime(&t->ups_ms[k], ev[k + 1], ev[k + 2]);
+    }
+    host_result->raised = h[0];
+    host_result->equal = h[1];
+    host_result->older = h[2];
+    host_result->inserted = m;
+    host_result->replaced = h[4];
+    host_result->evictions = h[5];
+    host_result->log_head = t->geo.log_head;
+    host_result->reserved = 0;
+    return 0;
+}
+
+int hkv_debug_upsert_phases(const hkv_table *t, float *ms5)
+{
+    if (!t || !ms5) return fail(-1, "upsert_phases: null argument");
+    if (!g_ups_phases) return fail(-1, "upsert_phases: HKV_UPSERT_PHASES is not set");
+    for (int k = 0; k < 5; ++k) ms5[k] = t->ups_ms[k];
+    return 0;
 }
 
 int hkv_hash_ids(const uint32_t *d_ids, uint64_t *d_keys_second, int64_t n, void *stream)

@@ -17,7 +17,8 @@ import numpy as np
 import torch
 
 from . import layout as L
-from .lib import ABI_VERSION, HkvBatchDesc, HkvCensus, HkvConfig, HkvError, HkvLayoutInfo, Membership, check, raw
+from .lib import (ABI_VERSION, HkvBatchDesc, HkvCensus, HkvConfig, HkvError, HkvLayoutInfo, HkvUpsertResult, Membership,
+                  check, raw)
 
 _L = raw()
 
@@ -610,6 +611,34 @@ class HermesKV:
         check(_L.hkv_table_install_async(self.h, ctypes.c_void_p(t.data_ptr()), n, ctypes.c_void_p(result.data_ptr()),
                                          ctypes.c_void_p(s)), "hkv_table_install_async")
         return InstallResult(result[:4])
+
+    # -- upsert (include/hermeskv.h, "Upsert")
+    def upsert(self, records, n: int | None = None, stream: torch.cuda.Stream | None = None) -> dict:
+        """hkv_table_upsert: install() of the n records (an Extract, or a uint8 device tensor of whole records, no
+        key twice among them) and then, for every record the install missed, in record order, the reference's
+        insert (mica_insert_one) of the entry that record stands for. Returns hkv_upsert_result as a dict: raised,
+        equal, older (the install's counts), inserted (its missed), replaced (inserts that took an in-use slot by
+        tag match: the key that slot led to is lost), evictions (inserts that found no slot) and log_head. Unlike
+        install() the call returns when its work on `stream` is done: the number of inserts is known only on the
+        device and the log head lives on the host. With nothing missed it is an install (an INLINE table stays
+        INLINE); otherwise the table goes to LOG first, as before a populate. num_keys follows the inserts, so a
+        later extract()'s default buffer holds them. Not for tables with RMWs."""
+        E = self.sizes.entry
+        t = records.tensor if isinstance(records, Extract) else records
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+        if n is None:
+            n = records.written if isinstance(records, Extract) else t.numel() // E
+        n = int(n)
+        assert 0 <= n and n * E <= t.numel()
+        out = HkvUpsertResult()
+        if n == 0:   # (an empty tensor has no address to pass)
+            return {name: self.log_head if name == "log_head" else 0 for name, _ in HkvUpsertResult._fields_[:7]}
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        self.launches += 1
+        check(_L.hkv_table_upsert(self.h, ctypes.c_void_p(t.data_ptr()), n, ctypes.byref(out), ctypes.c_void_p(s)),
+              "hkv_table_upsert")
+        self.num_keys += int(out.inserted)
+        return {name: int(getattr(out, name)) for name, _ in HkvUpsertResult._fields_[:7]}
 
     def device_index(self) -> int:
         return _L.hkv_device_index(self.h)

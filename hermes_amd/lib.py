@@ -69,6 +69,13 @@ class HkvInstallResult(ctypes.Structure):
                 ("missed", ctypes.c_uint64)]
 
 
+class HkvUpsertResult(ctypes.Structure):
+    """hkv_upsert_result (include/hermeskv.h, "Upsert"): 64 bytes, written to host memory"""
+    _fields_ = [("raised", ctypes.c_uint64), ("equal", ctypes.c_uint64), ("older", ctypes.c_uint64),
+                ("inserted", ctypes.c_uint64), ("replaced", ctypes.c_uint64), ("evictions", ctypes.c_uint64),
+                ("log_head", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
 class HkvPartRow(ctypes.Structure):
     """hkv_part_row (include/hermeskv.h, "Partitioned census and delta repair"): one partition's census"""
     _fields_ = [("digest_sum", ctypes.c_uint64), ("digest_xor", ctypes.c_uint64), ("keys", ctypes.c_uint64),
@@ -120,6 +127,9 @@ _L.hkv_table_census_parts_async.argtypes = [_P, ctypes.c_uint32, _P, _P]
 _L.hkv_part_rows_diff_async.argtypes = [_P, _P, ctypes.c_uint32, _P, _P, ctypes.c_int, _P]
 _L.hkv_table_extract_parts_async.argtypes = [_P, ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _P,
                                              ctypes.c_uint64, _P, _P]
+_L.hkv_upsert_result_bytes.restype = ctypes.c_uint32
+_L.hkv_table_upsert.argtypes = [_P, _P, ctypes.c_uint64, ctypes.POINTER(HkvUpsertResult), _P]
+_L.hkv_debug_upsert_phases.argtypes = [_P, ctypes.POINTER(ctypes.c_float)]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

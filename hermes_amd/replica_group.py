@@ -730,13 +730,40 @@ def group_census(kvs: HermesKV, group=None, live_ranks=None) -> dict:
             "not_valid": [r[3] for r in rows]}
 
 
+class _RecordSink:
+    """Where a repair's records go: HermesKV.install (insert False: today's path and today's dict), or
+    HermesKV.upsert, which also inserts the keys the table lacks. result(): the summed counts {raised, equal, older,
+    missed}; with insert, missed is 0 and inserted, replaced and evictions are added."""
+
+    def __init__(self, kvs: HermesKV, insert: bool, dev):
+        self.kvs, self.insert = kvs, bool(insert)
+        self.tot = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.ups = dict.fromkeys(("raised", "equal", "older", "inserted", "replaced", "evictions"), 0)
+
+    def __call__(self, records, n: int) -> None:
+        if not self.insert:
+            self.tot += self.kvs.install(records, n=n).tensor
+            return
+        r = self.kvs.upsert(records, n=n)
+        for k in self.ups:
+            self.ups[k] += r[k]
+
+    def result(self) -> dict:
+        if not self.insert:
+            return {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), self.tot.cpu().tolist())}
+        u = self.ups
+        return {"raised": u["raised"], "equal": u["equal"], "older": u["older"], "missed": 0,
+                "inserted": u["inserted"], "replaced": u["replaced"], "evictions": u["evictions"]}
+
+
 def _bucket_chunks(num_bkts: int, chunk_buckets: int | None):
     step = int(chunk_buckets) if chunk_buckets else int(num_bkts)
     assert step > 0
     return [(lo, min(lo + step, int(num_bkts))) for lo in range(0, int(num_bkts), step)]
 
 
-def resync(dst: HermesKV, src: HermesKV, chunk_buckets: int | None = None, min_ts: int = 0) -> dict:
+def resync(dst: HermesKV, src: HermesKV, chunk_buckets: int | None = None, min_ts: int = 0,
+           insert: bool = False) -> dict:
     """Repair a stale replica from a live one, both tables in this process (loopback groups, one-GPU tests): walk
     `src` in chunks of chunk_buckets buckets (default: the whole table at once), HermesKV.extract each chunk into
     one reused buffer and HermesKV.install it into `dst`, which may have another bucket count, log order or
@@ -745,14 +772,19 @@ def resync(dst: HermesKV, src: HermesKV, chunk_buckets: int | None = None, min_t
     eight keys per bucket, at most the source's keys). After a resync of a quiet group the two tables' census
     digests are equal. Sound only while `dst` takes no client operations; INVs it receives meanwhile are safe,
     the install being timestamp-guarded (an older record changes nothing). min_ts only saves volume -- there is
-    no global watermark in a per-key protocol. Membership re-admission is not done here."""
+    no global watermark in a per-key protocol. Membership re-admission is not done here.
+    insert=True: each chunk goes through HermesKV.upsert instead, which inserts the keys `dst` lacks as the
+    reference inserts (include/hermeskv.h, "Upsert"); `missed` is then 0 and inserted, replaced and evictions are
+    added to the dict. `dst` may then be empty (created with populate=False): a rebuild. What can still leave the
+    tables' digests apart: `dst` is newer in a key (`older`), or keys were lost to the lossy index -- an insert
+    that `replaced` a live slot of the same tag, or an eviction; both are counted, never hidden."""
     assert dst.sizes == src.sizes, "records of one entry size only"
     chunks = _bucket_chunks(src.cfg.num_bkts, chunk_buckets)
     cap = max(1, min(int(src.num_keys), 8 * max(hi - lo for lo, hi in chunks)))
     dev = torch.device("cuda", src.device)
     buf = torch.empty(cap * src.sizes.entry, dtype=torch.uint8, device=dev)
     res = torch.empty(2, dtype=torch.int64, device=dev)
-    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    sink = _RecordSink(dst, insert, dev)
     records = scanned = 0
     for lo, hi in chunks:
         x = src.extract((lo, hi), min_ts, out=buf, result=res)
@@ -760,20 +792,22 @@ def resync(dst: HermesKV, src: HermesKV, chunk_buckets: int | None = None, min_t
         assert h["records"] <= cap, "more live keys in a chunk than slots"
         records, scanned = records + h["records"], scanned + h["scanned_keys"]
         if h["records"]:
-            tot += dst.install(x, n=h["records"]).tensor
-    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+            sink(x, h["records"])
+    out = sink.result()
     out.update(records=records, scanned_keys=scanned)
     return out
 
 
-def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buckets: int | None, min_ts: int = 0) -> dict:
+def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buckets: int | None, min_ts: int = 0,
+                 insert: bool = False) -> dict:
     """resync() across ranks. Collective: every rank of `group` calls it with the same arguments and its own table
     (tables of one entry size; bucket counts may differ -- the chunks walk the source's, whose count is broadcast
     first). Per chunk the source rank extracts and broadcasts the record count, then the records (CUDA tensors
     through torch.distributed: gloo and NCCL / RCCL alike); only the ranks in stale_ranks install, the others
     just take part in the broadcasts. Returns this rank's summed install counts (zeros where it did not install)
     plus records and scanned_keys of the source. The same conditions as resync(): a stale rank takes no client
-    operations meanwhile, and nobody is re-admitted to the membership here."""
+    operations meanwhile, and nobody is re-admitted to the membership here. insert=True: the stale ranks upsert
+    (resync()'s insert: inserted, replaced and evictions in the dict, missed 0; a stale rank may be empty)."""
     import torch.distributed as dist
     rank = dist.get_rank(group)
     src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
@@ -788,7 +822,7 @@ def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buck
     cap = max(1, min(src_keys, 8 * max(hi - lo for lo, hi in chunks)))
     buf = torch.empty(cap * E, dtype=torch.uint8, device=dev)
     res = torch.zeros(2, dtype=torch.int64, device=dev)
-    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    sink = _RecordSink(kvs, insert, dev)
     records = scanned = 0
     for lo, hi in chunks:
         if rank == source_rank:
@@ -801,8 +835,8 @@ def group_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, chunk_buck
             continue
         dist.broadcast(buf[:n * E], src, group=group)
         if rank in stale:
-            tot += kvs.install(buf, n=n).tensor
-    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+            sink(buf, n)
+    out = sink.result()
     out.update(records=records, scanned_keys=scanned)
     return out
 
@@ -851,7 +885,8 @@ def _log2_buckets(num_bkts: int) -> int:
     return int(num_bkts).bit_length() - 1
 
 
-def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chunk_buckets: int | None = None) -> dict:
+def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chunk_buckets: int | None = None,
+                 insert: bool = False) -> dict:
     """resync() that ships only the partitions that differ (include/hermeskv.h, "Partitioned census and delta
     repair"), both tables in this process. In this order: HermesKV.census_parts of both tables at part_bits
     (default: min(20, log2 of the smaller bucket count); at most log2 of either bucket count, so that every key of a
@@ -866,7 +901,11 @@ def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chu
     (its record counts as `missed`). Equal keys of a differing partition are shipped too and count as `equal`: the
     install is timestamp-guarded. Every limit of resync() holds: sound only while `dst` takes no client operations
     (INVs it receives meanwhile are safe); nothing is inserted; nobody is re-admitted to the membership; extract and
-    install refuse tables with RMWs."""
+    install refuse tables with RMWs.
+    insert=True: the records go through HermesKV.upsert, which inserts the keys `dst` lacks (include/hermeskv.h,
+    "Upsert"); `missed` is 0 and inserted, replaced and evictions are added. A partition can then still be in
+    unresolved for two reasons: `dst` is newer in a key (`older`), or keys were lost to `replaced` / `evictions`
+    (the reference's lossy index: an insert took a live slot). Such partitions are reported, never hidden."""
     assert dst.sizes == src.sizes, "records of one entry size only"
     if part_bits is None:
         part_bits = min(20, _log2_buckets(min(src.cfg.num_bkts, dst.cfg.num_bkts)))
@@ -875,7 +914,7 @@ def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chu
     rows = src.census_parts(part_bits).tensor
     mask, count = part_diff(rows, dst.census_parts(part_bits))
     n, differing = _selected_keys(rows, mask, count)
-    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    sink = _RecordSink(dst, insert, dev)
     records = scanned = 0
     if n:
         buf = torch.empty(n * src.sizes.entry, dtype=torch.uint8, device=dev)
@@ -885,16 +924,16 @@ def delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chu
             h = x.host()
             records, scanned = records + h["records"], scanned + h["scanned_keys"]
             if h["records"]:
-                tot += dst.install(x, n=h["records"]).tensor
+                sink(x, h["records"])
         assert records == n, "the selected partitions' key counts are the masked extract's records"
-    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+    out = sink.result()
     out.update(records=records, scanned_keys=scanned, partitions=1 << part_bits, differing_before=differing)
     out.update(_delta_verify(dst, rows, part_bits))
     return out
 
 
 def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part_bits: int | None,
-                       chunk_buckets: int | None) -> dict:
+                       chunk_buckets: int | None, insert: bool = False) -> dict:
     """delta_resync() across ranks. Collective: every rank of `group` calls it with the same arguments and its own
     table (tables of one entry size; bucket counts may differ). part_bits None: min(20, log2 of the smallest bucket
     count of the group), agreed by an all_reduce. The source rank broadcasts its partition rows; each stale rank
@@ -908,7 +947,9 @@ def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part
     the keys of the partitions only another stale rank differed in. The conditions are delta_resync()'s: a stale
     rank takes no client operations meanwhile, nothing is inserted, nobody is re-admitted to the membership here,
     no tables with RMWs; a partition that still differs (the rank is newer in a key: `older`; it lacks or shadows
-    a key: `missed`) is reported in unresolved."""
+    a key: `missed`) is reported in unresolved. insert=True: the stale ranks upsert (delta_resync()'s insert:
+    inserted, replaced and evictions in the dict, missed 0); a partition still in unresolved is then one where the
+    rank is newer in a key or lost keys to `replaced` / `evictions`."""
     import torch.distributed as dist
     rank = dist.get_rank(group)
     src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
@@ -934,7 +975,7 @@ def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part
     differing = count.clone()
     dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=group)
     n, selected = _selected_keys(rows, mask, (mask != 0).sum().reshape(1))
-    tot = torch.zeros(4, dtype=torch.int64, device=dev)
+    sink = _RecordSink(kvs, insert, dev)
     records = scanned = 0
     if n:
         buf = torch.empty(n * E, dtype=torch.uint8, device=dev)
@@ -950,8 +991,8 @@ def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part
                 continue
             dist.broadcast(buf[:m * E], src, group=group)
             if rank in stale:
-                tot += kvs.install(buf, n=m).tensor
-    out = {k: int(v) for k, v in zip(("raised", "equal", "older", "missed"), tot.cpu().tolist())}
+                sink(buf, m)
+    out = sink.result()
     out.update(records=records, scanned_keys=scanned, partitions=P, selected=selected,
                differing_before=int(differing.cpu()[0]))
     out.update(_delta_verify(kvs, rows, part_bits) if rank in stale else {"differing_after": 0, "unresolved": []})

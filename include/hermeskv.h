@@ -374,7 +374,8 @@ int hkv_table_census(hkv_table *t, hkv_census *host_out);
  * hermes_exec_inv does (VALID at the end when the source was VALID); a record of equal timestamp touches only
  * what an INV and a VAL of that timestamp touch; an older record changes nothing; a key the source caught
  * mid-write (state not VALID) is left not VALID at that timestamp -- the message a shadow replica would have
- * received; a key the target does not hold is a miss (there are no inserts after populate). The lock byte,
+ * received; a key the target does not hold is a miss (there are no inserts after populate; hkv_table_upsert, below, is the
+ * install that inserts such a key). The lock byte,
  * ack_bv, op buffer index and last-local-write timestamp are left as those two batches leave them, and the
  * per-line F/X/Y/T words of the batch engines are not touched. On an INLINE table the inline keys are read and
  * written in their lines only; nothing is converted and the layout counters do not move.
@@ -449,7 +450,8 @@ int hkv_table_install_async(hkv_table *t, const void *d_records, uint64_t n, hkv
  * of a repair holds: the target takes no client operations meanwhile, nothing is inserted, nobody is re-admitted
  * to the membership, and extract and install refuse RMW tables. A partition can still differ afterwards, and is
  * then reported, not hidden; two causes are known: the target is newer in a key (that record counts as `older`),
- * or the target lacks the key or shadows it behind another (that record counts as `missed`). */
+ * or the target lacks the key or shadows it behind another (that record counts as `missed`; a delta repair that
+ * upserts instead of installing, hkv_table_upsert below, inserts it). */
 typedef struct hkv_part_row {
     uint64_t digest_sum, digest_xor;   /* the census's, over the partition's live keys */
     uint64_t keys;                     /* live keys of the partition */
@@ -462,6 +464,78 @@ int hkv_part_rows_diff_async(const hkv_part_row *d_a, const hkv_part_row *d_b, u
 int hkv_table_extract_parts_async(hkv_table *t, uint32_t part_bits, const uint8_t *d_part_mask,
                                   uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, void *d_records,
                                   uint64_t record_cap, hkv_extract_result *d_result, void *stream);
+
+/* Upsert (ABI 10, functions only): install records and insert the keys the table lacks. The install and the delta
+ * repair above stop at a key the target does not hold; hkv_table_upsert takes the same records (device memory,
+ * 16-byte aligned, n records of E bytes, no key twice -- the caller's guarantee -- and never written by the call)
+ * and inserts those keys as the reference inserts: mica_insert_one. The result goes to HOST memory and the call
+ * returns when its work on `stream` is done, as hkv_table_populate does: the table's log head lives on the host and
+ * the number of inserts is known only on the device.
+ *
+ * An upsert equals the reference doing the following.
+ *   1. Install. The install of the n records exactly as defined under "Replica repair": one `invs` batch, then one
+ *      `vals` batch. A record whose INV comes back ST_MISS is missed; the missed set is decided here, against the
+ *      table as it was before the call.
+ *   2. Insert. Then, for each missed record in record order: mica_insert_one (mica.c:78-146) of the entry image
+ *      that spacetime_populate_fixed_len(kv, ., KVS_VALUE_SIZE) builds (spacetime.c:17-68: opcode ST_OP_PUT, val_len
+ *      KVS_VALUE_SIZE >> SHIFT_BITS, state VALID, last writer 127, op buffer index 255, timestamp (0, 255); the
+ *      fields the reference leaves uninitialised -- ack_bv, RMW flag, last-local-write timestamp -- zero, as a
+ *      populate writes them), with two changes: bytes 8..15 are the record's key with bytes 0..7 zero (a record
+ *      carries no key_first, and no lookup reads it), and the value bytes are the record's value. Immediately
+ *      afterwards the reference applies that record's INV and, if its state byte is VALID, its VAL, as one-element
+ *      batches, which find the entry just inserted (*). So the entry that lands in the log is a pure function of the
+ *      record, also when a later insert of the same call replaces its slot: a record newer than (0, 255) leaves
+ *      its timestamp, last writer = its cid, val_len KVS_VALUE_SIZE as an INV writes it, and state VALID when the
+ *      record was VALID, else INVALID (a key the source held mid-write arrives INVALID with the writer's cid as last
+ *      writer); a record of timestamp (0, 255) -- a key never written -- leaves the populate image; an older one
+ *      (version 0, cid < 255) leaves the populate image too, VALID.
+ *      The i-th missed record, counting in record order, takes the i-th log offset mica_insert_one would hand out
+ *      from the current head: the head advances by E (the 8-byte rounding of the copied length) per insert and
+ *      wraps once, when no more than KVS_VALUE_SIZE + 32 bytes remain below log_cap; after that wrap the unsigned
+ *      test never fires again. Slot choice is the reference's: the last slot of the bucket that is empty or carries
+ *      the key's tag, else slot tag & 7. Within a bucket the inserts are applied in record order.
+ *      (*) The lookup takes the first in-use slot with the key's tag, the insert the last slot that is empty or
+ *      has it. On a table filled by inserts alone they are the same slot: the slots fill from slot 7 downwards, so
+ *      the empty ones lie below the ones in use, and a tag is never in use twice in a bucket.
+ * Index, log and log head after the call are therefore bytes a model can predict (tests/upsert_model.py): they do
+ * not depend on grid size, block order or atomics.
+ *
+ * hkv_upsert_result (64 bytes): raised, equal, older -- the install's counts; inserted -- the install's `missed`;
+ * replaced -- inserts that took an in-use slot by tag match: the key that slot pointed to, if it was live and a
+ * different key, is no longer reachable (the reference's lossy index; it is what makes ids 631343 / 722989 / 864394
+ * miss at 1M keys); evictions -- inserts that found no slot and took slot tag & 7 (also added to what
+ * hkv_num_index_evictions reports); log_head -- the log head after the call; one reserved word, zero.
+ *
+ * Residency. Step 1 runs on the table as it is, LOG or INLINE, exactly like the install. If nothing was missed the
+ * call ends there and is indistinguishable from an install: conversions and inline_launches do not move. If
+ * anything was missed the table goes to LOG first (as before a populate) and the inserts go into index and log;
+ * the next inline-capable launch reconverts by the sticky preference, as after a populate. Inserting into the
+ * lines in place is out of scope: every insert into a bucket that is not full takes a slot below the ones in use
+ * and so would change the bucket's inline key.
+ * The table's insert count and log head advance; a wrapped log makes the table ineligible for the inline layout,
+ * as after a populate. The per-line F/X/Y/T words of the batch engines are not touched (DESIGN 4.12 has the
+ * argument why a line first used, or reused after a wrap, needs nothing).
+ * Ordering: a live serving kernel is stopped and the call is ordered after the table's last stream, as the other
+ * table calls; one caller at a time per table.
+ * Refusals, with a negative code and a message that names `upsert`, before anything is launched: a NULL table,
+ * records (whatever n is) or result; a table with rmw_enabled (the install's reason); records not 16-byte aligned;
+ * n above 2^31 - 1. Every entry size is supported: 64 B and E = 64 + 64 c. Out of scope: re-admitting the rebuilt
+ * replica to the membership, and a client-facing insert opcode in the batch path (the reference has none). */
+typedef struct hkv_upsert_result {
+    uint64_t raised, equal, older;   /* the install's counts, against the table as it was before the call */
+    uint64_t inserted;               /* the install's missed: every one of them was inserted */
+    uint64_t replaced;               /* inserts that took an in-use slot by tag match */
+    uint64_t evictions;              /* inserts that found no slot (slot tag & 7) */
+    uint64_t log_head;               /* the log head after the call */
+    uint64_t reserved;               /* zero */
+} hkv_upsert_result;
+uint32_t hkv_upsert_result_bytes(void);   /* sizeof(hkv_upsert_result) = 64, for bindings */
+int hkv_table_upsert(hkv_table *t, const void *d_records, uint64_t n, hkv_upsert_result *host_result, void *stream);
+/* timing hook (tools/rebuild_bench.py): with HKV_UPSERT_PHASES set in the environment every upsert records an event
+ * between its phases, and this returns the table's last upsert's times in ms: the install pass, the scan and the
+ * pairs, the sort, the bucket replay, the log writes (the last four zero when nothing was inserted). An error
+ * without the variable. */
+int hkv_debug_upsert_phases(const hkv_table *t, float *ms5);
 
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
