@@ -40,7 +40,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "hkv_batch_dev.h"   // BatchArgs, BatchPlan; k_small is in hkv_batch_small.hip
+#include "hkv_batch_dev.h"   // BatchArgs, BatchPlan, the shared helpers; see its file map
 
 namespace hkv {
 
@@ -52,45 +52,6 @@ namespace hkv {
 __host__ __device__ constexpr int rounds_for(int type, bool rmw)
 {
     return type == kVals || (type == kLocal && !rmw) ? 0 : 2;
-}
-
-// The state a key is in after any mutation by an element of this batch type, when that state
-// makes every later element of the launch a non-mutating one whose result depends on the state
-// alone (rounds_for == 0):
-//   local, RMWs off: a mutation is a PUT (update_actions -> WRITE, hermesKV.c:100-141) or a GET
-//     replay (-> REPLAY, :155-175); under either, GETs stall (:279-282) and PUTs stall (:352-354).
-//   VALs: hermes_exec_val only ever sets VALID (:676-703) and its opcode is VAL_SUCCESS whatever
-//     the state; under VALID no VAL mutates.
-template <int TYPE>
-__device__ __forceinline__ uint8_t absorbing_state()
-{
-    return TYPE == kVals ? kValid : kWrite;
-}
-
-// The meta every element after F (its key's only mutation in the launch) runs against, from S_0.
-// Without the skew optimisations only the absorbing state matters. With them, a stalled GET or
-// PUT also reads the timestamp and tells WRITE from REPLAY (hermesKV.c:196-238), so the meta is
-// S_1 itself: after a PUT, update_actions' WRITE with version + 2 and this machine's cid
-// (hermesKV.c:100-141, RMWs off); after a GET replay, REPLAY with the timestamp unchanged
-// (:155-175). f_is_put: F is known to be a PUT (else its opcode is read).
-template <int TYPE>
-__device__ __forceinline__ Meta after_first(const BatchArgs &a, const Meta &m0, uint32_t f, int f_is_put)
-{
-    Meta m1 = m0;
-    m_set_state(m1, absorbing_state<TYPE>());
-    if (TYPE != kLocal || a.g.skew == 0) return m1;
-    uint8_t foc = f_is_put ? (uint8_t)kOpPut : a.elems[(int64_t)f * a.esz + 8];
-    if (a.hx && !f_is_put) {   // patch_in_resolve: F's op may not be patched yet (its patch is valid at byte 14)
-        const uint64_t pb = *reinterpret_cast<const uint64_t *>(a.patch + (int64_t)f * 16 + 8);
-        if ((pb >> 48) & 0xFFu) foc = (uint8_t)pb;
-    }
-    if (foc != kOpGet) {
-        m1.ver += 2;
-        m_set_cid(m1, (uint8_t)a.g.machine_id);
-    } else {
-        m_set_state(m1, kReplay);
-    }
-    return m1;
 }
 
 // INV direct path (INV launches without RMWs, fewer than 2^23 elements). Without RMWs,
@@ -143,82 +104,6 @@ __device__ __forceinline__ uint8_t inv_opcode(uint8_t in, bool oog)
     return oog ? kInvOutOfGroup : (in == kOpInvAbort || in == kInvOutOfGroup) ? in : kInvSuccess;
 }
 
-// The batch holding element i and its first element: i / stride, or for a packed launch the last
-// batch whose offset is <= i (empty batches share their successor's offset)
-__device__ __forceinline__ int32_t batch_of(const BatchArgs &a, int64_t i, int64_t &start)
-{
-    if (!a.offsets) {
-        const int32_t b = (int32_t)(i / a.stride);
-        start = (int64_t)b * a.stride;
-        return b;
-    }
-    int lo = 0, hi = a.n_batches - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (a.offsets[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    start = a.offsets[lo];
-    return lo;
-}
-
-__device__ __forceinline__ void elem_at(const BatchArgs &a, uint32_t i, uint8_t *&x, uint8_t &idx, Ctx &c)
-{
-    c.rw = nullptr;
-    c.rws = nullptr;
-    idx = 0;
-    if (a.rw || !a.offsets) {  // packed INV / VAL elements need neither (exec_inv / exec_val)
-        int64_t start;
-        const int32_t b = batch_of(a, i, start);
-        idx = (uint8_t)(i - start);
-        c.rw = a.rw ? a.rw + (int64_t)b * a.rw_stride : nullptr;
-        c.rws = a.rws ? a.rws + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
-        c.rwo = a.rwo ? a.rwo + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
-    }
-    x = a.elems + (int64_t)i * a.esz;
-}
-
-// the state mirror of a local launch: written by whichever pass finishes the element
-__device__ __forceinline__ void note_state(const BatchArgs &a, int64_t i, const uint8_t *x)
-{
-    if (a.state_out) a.state_out[i] = x[9];
-}
-
-// Inline instances (IL): an entry id of the local launch's scratch carries "this key's entry lives in its
-// bucket's line" in bit 31 (ids stay below it while log_cap <= kInlineMaxLog). A key's identity -- F/X/Y/T
-// words, phys_of, fw_index -- stays its log offset; only the bytes' home differs, and that is a function of the
-// bucket, so of the key, which every element, entry image and shadow holds.
-constexpr uint32_t kEntInline = 0x80000000u;
-template <bool IL>
-__device__ __forceinline__ uint32_t ent_id(uint32_t e) { return IL ? e & ~kEntInline : e; }
-template <bool IL>
-__device__ __forceinline__ uint8_t *entry_home(const BatchArgs &a, uint32_t e, uint64_t key)
-{
-    if (IL && (e & kEntInline)) return line_entry(a.line, a.g, key);
-    return entry_of(a, ent_id<IL>(e));
-}
-// Live entries never overlap and are at least 64 B long, so their first 64-B lines are distinct.
-// The F word of line l sits at l * odd mod 2^k (a bijection on the log's 2^k lines): keys that are
-// neighbours in the log -- the hottest ids of a populated table are -- get F words on different
-// lines, and memory-side atomics on one line serialise.
-__device__ __forceinline__ uint32_t fw_index(const BatchArgs &a, uint64_t phys)
-{
-    return (uint32_t)(((phys >> 6) * 0x9E3779B1ull) & a.fw_mask);
-}
-__device__ __forceinline__ unsigned long long *fw_of(const BatchArgs &a, uint32_t e) { return a.fw + fw_index(a, phys_of(a, e)); }
-
-__device__ __forceinline__ uint32_t first_cand(unsigned long long f, uint32_t rtag)
-{
-    return (uint32_t)(f >> 32) == ~rtag ? (uint32_t)f : kNone;
-}
-
-// F_r: atomicMin of ((~round tag) << 32 | element). The load filters most offers of a hot key:
-// F only falls, and elements are dispatched roughly in element order.
-__device__ __forceinline__ void offer(unsigned long long *f, uint32_t rtag, uint32_t i)
-{
-    const unsigned long long v = ((unsigned long long)(~rtag) << 32) | i;
-    if (v < __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(f, v);
-}
-
 // Wave-aggregated atomicAdd(&arr[j], 1): one atomic per distinct j in the wave; each active lane
 // gets its own ticket. All 64 lanes must call it.
 __device__ __forceinline__ uint32_t agg_ticket(uint32_t *arr, uint32_t j, bool active)
@@ -256,80 +141,6 @@ __device__ __forceinline__ void resolve_elem(const BatchArgs &a, uint32_t i, uin
     if (a.error_flags && !meta_equal(t, m)) atomicOr(a.error_flags, 1u);
 }
 
-__device__ __forceinline__ uint8_t *shadow_of(const BatchArgs &a, uint32_t i)
-{
-    return a.shadow + (size_t)i * a.g.entry_size;
-}
-
-// entries and shadows are 8-byte aligned and a multiple of 8 long: 16-B words, then one 8-B word
-__device__ __forceinline__ void copy_entry(uint8_t *dst, const uint8_t *src, uint32_t bytes)
-{
-    struct __attribute__((aligned(8))) W16 {
-        uint64_t a, b;
-    };
-    uint32_t o = 0;
-    for (; o + 16 <= bytes; o += 16) *reinterpret_cast<W16 *>(dst + o) = *reinterpret_cast<const W16 *>(src + o);
-    if (o < bytes) *reinterpret_cast<uint64_t *>(dst + o) = *reinterpret_cast<const uint64_t *>(src + o);
-}
-
-// The round's first candidate of a key: S_r (read from src: the entry in round 0, the previous
-// round's shadow later) -> S_{r+1}, written to the element's own shadow image, so the round's
-// other elements, resolved concurrently, still read S_r. Later rounds read the shadow; the key's
-// last shadow is committed to the entry once, by k_commit.
-template <int TYPE, int SV>
-__device__ __forceinline__ void apply_to_shadow(const BatchArgs &a, uint8_t *x, uint32_t i, const uint8_t *src)
-{
-    uint8_t *sh = shadow_of(a, i);
-    Meta m;
-    meta_load(src, m);
-    if (SV == 31) {  // 64-B entries and shadows are 16-byte aligned
-        const uint4 *s4 = reinterpret_cast<const uint4 *>(src);
-        uint4 *d4 = reinterpret_cast<uint4 *>(sh);
-        const uint4 w0 = s4[0], w1 = s4[1], w2 = s4[2], w3 = s4[3];
-        d4[0] = w0;
-        d4[1] = w1;
-        d4[2] = w2;
-        d4[3] = w3;
-    } else {
-        copy_entry(sh, src, a.g.entry_size);
-    }
-    Ctx c = make_ctx(a);
-    uint8_t *xg;
-    uint8_t idx;
-    elem_at(a, i, xg, idx, c);
-    // x: the element's LDS copy (k_resolve0), or null: the element in global memory. Two calls,
-    // not one on a select of the two, so each keeps its address space (no flat accesses).
-    if (x) dispatch<SV>(TYPE, x, sh, idx, m, c);
-    else dispatch<SV>(TYPE, xg, sh, idx, m, c);
-    meta_store(sh, m);
-}
-
-// apply_to_shadow for big entries, by the whole wave (every lane calls it; cand: this lane's element
-// is its key's first candidate, src its S_r): the wave copies S_r into the candidates' shadows
-// (wave_block_copies), then each candidate runs its exec function on its shadow with the value
-// copy recorded in vc (made by wave_value_copies after it), instead of one lane copying 320 + 287
-// bytes in dependent steps while the rest of its wave waits.
-__device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *src, uint32_t bytes);
-template <int TYPE, int SV>
-__device__ __forceinline__ void apply_to_shadow_wave(const BatchArgs &a, bool cand, uint32_t i, const uint8_t *src,
-                                                     VCopy &vc, uint8_t *xl = nullptr, bool use_xl = false)
-{
-    uint8_t *sh = cand ? shadow_of(a, i) : nullptr;
-    wave_block_copies(sh, src, a.g.entry_size);
-    __threadfence_block();   // the shadows' bytes before any lane reads or rewrites them
-    if (!cand) return;
-    Meta m;
-    meta_load(src, m);
-    Ctx c = make_ctx(a);
-    c.vc = &vc;
-    uint8_t *xg;
-    uint8_t idx;
-    elem_at(a, i, xg, idx, c);
-    if (use_xl) dispatch<SV>(TYPE, xl, sh, idx, m, c);   // xl: the element's patched copy (k_resolve0_direct)
-    else dispatch<SV>(TYPE, xg, sh, idx, m, c);
-    meta_store(sh, m);
-}
-
 // ------------------------------------------------------------------ k_lookup (+ round 0 candidates)
 // Four lanes per element: each lane reads 16 bytes (two slots) of the element's 64-byte bucket,
 // so one load instruction covers a whole bucket line per element. Slots are searched in the
@@ -365,7 +176,6 @@ __device__ __forceinline__ uint64_t patched_hdr(uint64_t h, uint64_t pb)
     const uint64_t low = (pb & 0xFFu) | ((uint64_t)kNew << 8) | (((pb >> 8) & 0xFFu) << 16);
     return reset ? low : (low | (h & ~0xFFFFFFull));
 }
-__device__ __forceinline__ bool patch_valid(uint64_t pb);
 
 // Local launches with RMWs: how a round-0 candidate (would_mutate against S_0) changes its key, from its
 // header word h (bytes 8..15) and S_0 -- bits 0..1: 1 update_actions (a PUT, or an RMW from VALID;
@@ -412,89 +222,11 @@ __device__ __forceinline__ Meta after_first_rmw(const BatchArgs &a, const Meta &
 }
 
 constexpr int64_t kLookupHead = 8192;
-constexpr int kLookupPair = 2;
-// Four lanes (q = lane & 3) look up kLookupPair keys side by side: the 64-B bucket (16 B per
-// lane), the reference's slot order (first tag match, hermesKV.c:954-975), the log window
-// (:969-970), then each lane's 16 B of the 64-B log line (bytes 16q..16q+15). All four lanes of a
-// group call it with the same arguments.
-// IL (the inline instances, a.line set): the bucket is the first half of its 128-B line and each lane loads its
-// 16 B of the second half -- the inline key's entry -- in the same step; a hit on the flagged slot takes those
-// bytes, any other hit loads the log line as before. home: where the hit's entry bytes live (writes go there);
-// inl: the hit is its bucket's inline key. phys stays the log offset either way (the key's identity).
-template <int P = kLookupPair, bool IL = false, bool F = false>
-__device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
-                                            int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv,
-                                            uint8_t **home, bool *inl)
-{
-    uint4 v[P], ev[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        if (IL) {
-            const uint4 *l = line_words(a.line, bucket_of(a.g, key[k]));
-            v[k] = probe[k] ? l[q] : make_uint4(0u, 0u, 0u, 0u);
-            ev[k] = probe[k] ? l[4 + q] : make_uint4(0u, 0u, 0u, 0u);
-        } else {
-            v[k] = probe[k] ? bucket_words(a.index, bucket_of(a.g, key[k]))[q] : make_uint4(0u, 0u, 0u, 0u);
-        }
-    }
-    bool il[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        // group_probe (hkv_table_dev.h) with its tag test and slot mask written out: through slot_matches or
-        // group_slots k_local_pre and k_unique_rows change their register counts (profiles/table_dev_registers.txt)
-        const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
-        const uint32_t tag = key_tag(key[k]);
-        const bool mt0 = probe[k] && (s0 & 1u) && ((uint32_t)(s0 >> 1) & 0x7FFFFFu) == tag;
-        const bool mt1 = probe[k] && (s1 & 1u) && ((uint32_t)(s1 >> 1) & 0x7FFFFFu) == tag;
-        const uint32_t g0 = (uint32_t)(__ballot(mt0) >> gbase) & 0xFu;
-        const uint32_t g1 = (uint32_t)(__ballot(mt1) >> gbase) & 0xFu;
-        uint32_t o = 0;  // bit 2*l + j: slot 2*l + j matches
-#pragma unroll
-        for (int l = 0; l < 4; ++l) o |= ((g0 >> l) & 1u) << (2 * l) | ((g1 >> l) & 1u) << (2 * l + 1);
-        const int first = o ? __ffs(o) - 1 : 0;
-        const uint64_t raw = group_slot_word(slot_off_raw(s0), slot_off_raw(s1), first), off = off_of<IL>(raw);
-        ok[k] = probe[k] && o && in_log_window(a.g, off);
-        phys[k] = off & a.g.log_mask;
-        il[k] = off_is_inline<IL>(raw) && ok[k];
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        if (IL) {
-            ln[k] = ev[k];
-            if (!il[k]) ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
-            if (home) home[k] = il[k] ? line_entry(a.line, a.g, key[k]) : a.log + phys[k];
-            if (inl) inl[k] = il[k];
-        } else {
-            ln[k] = ok[k] ? reinterpret_cast<const uint4 *>(a.log + phys[k])[q] : make_uint4(0u, 0u, 0u, 0u);
-            if (home) home[k] = a.log + phys[k];
-            if (inl) inl[k] = false;
-        }
-        if (F) fwv[k] = ok[k] && q == 0 ? a.fw[fw_index(a, phys[k])] : ~0ull;
-    }
-}
 
-template <int P = kLookupPair, bool IL = false>
-__device__ __forceinline__ void lookup_pair(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
-                                            int gbase, bool *ok, uint64_t *phys, uint4 *ln, uint8_t **home = nullptr,
-                                            bool *inl = nullptr)
-{
-    lookup_core<P, IL, false>(a, key, probe, q, gbase, ok, phys, ln, nullptr, home, inl);
-}
-
-// lookup_pair that also loads each hit's F word beside its log line (lane q == 0; ~0 for a miss), so a
-// key's F costs no dependent load after the line (k_local_fused)
-template <int P, bool IL = false>
-__device__ __forceinline__ void lookup_pair_f(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
-                                              int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv,
-                                              uint8_t **home = nullptr, bool *inl = nullptr)
-{
-    lookup_core<P, IL, true>(a, key, probe, q, gbase, ok, phys, ln, fwv, home, inl);
-}
-
-
-template <int P = kLookupPair, bool IL = false>
+template <bool IL = false>
 __global__ __launch_bounds__(256) void k_lookup(BatchArgs a, int64_t i_begin, int64_t i_end)
 {
+    constexpr int P = 1;   // elements per lane group (launch_rounds has the measurements)
     const int q = threadIdx.x & 3;
     const int lane = threadIdx.x & 63;
     const int gbase = lane & ~3;
@@ -1159,7 +891,7 @@ __device__ __forceinline__ void wave_value_words_n(const VCopy &v, uint32_t n)
 // by words where the value allows it; values over 496 B take the byte-wise copies
 __device__ __forceinline__ void wave_value_copies(const VCopy &v, uint32_t n, int batch)
 {
-    if (n <= 8 * 62) {   // nw + 1 <= 64 source words
+    if (n <= kWaveWordsMaxValue) {
         if (batch == 1) wave_value_words_n<1>(v, n);
         else wave_value_words_n<kVcBatch>(v, n);
         return;
@@ -1168,12 +900,16 @@ __device__ __forceinline__ void wave_value_copies(const VCopy &v, uint32_t n, in
     else wave_value_copies_n<kVcBatch>(v, n);
 }
 
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src)
+{
+    return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, src, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64) << 32);
+}
+
 // Whole-wave copies of `bytes` (a multiple of 8, 8-byte aligned ends) recorded one per lane (dst
 // null: none): C = bytes / 16 rounded up lanes per copy move 16 B each, 64 / C copies per
 // instruction, and kBcRounds instructions' loads are issued before their stores. Every lane of the
 // wave calls it.
 constexpr int kBcRounds = 2;
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src);
 __device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *src, uint32_t bytes)
 {
     struct __attribute__((aligned(8))) W16 {
@@ -1234,6 +970,31 @@ __device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *s
     }
 }
 
+// apply_to_shadow for big entries, by the whole wave (every lane calls it; cand: this lane's element
+// is its key's first candidate, src its S_r): the wave copies S_r into the candidates' shadows
+// (wave_block_copies), then each candidate runs its exec function on its shadow with the value
+// copy recorded in vc (made by wave_value_copies after it), instead of one lane copying 320 + 287
+// bytes in dependent steps while the rest of its wave waits.
+template <int TYPE, int SV>
+__device__ __forceinline__ void apply_to_shadow_wave(const BatchArgs &a, bool cand, uint32_t i, const uint8_t *src,
+                                                     VCopy &vc, uint8_t *xl = nullptr, bool use_xl = false)
+{
+    uint8_t *sh = cand ? shadow_of(a, i) : nullptr;
+    wave_block_copies(sh, src, a.g.entry_size);
+    __threadfence_block();   // the shadows' bytes before any lane reads or rewrites them
+    if (!cand) return;
+    Meta m;
+    meta_load(src, m);
+    Ctx c = make_ctx(a);
+    c.vc = &vc;
+    uint8_t *xg;
+    uint8_t idx;
+    elem_at(a, i, xg, idx, c);
+    if (use_xl) dispatch<SV>(TYPE, xl, sh, idx, m, c);   // xl: the element's patched copy (k_resolve0_direct)
+    else dispatch<SV>(TYPE, xg, sh, idx, m, c);
+    meta_store(sh, m);
+}
+
 // patch_in_resolve (big local launches with refill patches, a.hx set; launch_batch): k_lookup read each
 // patch beside the op's header, so a patched element runs its exec function on a copy of its op's first 24
 // bytes in LDS -- key and header word as patched (k_lookup), flags from the patch -- and this pass writes the
@@ -1242,10 +1003,6 @@ __device__ __forceinline__ void wave_block_copies(uint8_t *dst, const uint8_t *s
 // 64-byte blocks are written whole (a block written with holes costs HBM a read-modify-write:
 // tools/write_bench.hip). The refill's own pass over the slab (k_refill_st_w) goes, and this pass reads
 // no op line: the header came with k_lookup's read, a write's value is the patch's fill byte.
-__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src)
-{
-    return (uint64_t)(uint32_t)__shfl((int)(uint32_t)v, src, 64) | ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(v >> 32), src, 64) << 32);
-}
 // Ops whose every byte is known (k_resolve0_direct's whole ones: key h0, header h1, flags and fill byte fl, the
 // fill, the last word lw; nw 8-byte words) written by the whole wave: (nw + 1) / 2 lanes per op, 16 B each, so
 // one store instruction writes 64 / that many ops contiguously. Every lane calls it.
@@ -1408,102 +1165,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
 }
 
-// ------------------------------------------------------------------ local launches: direct path
-// Local batches without RMWs, 56-B ops and 64-B entries (configs[1]). Under these, an element's
-// key can only be mutated by a PUT (hermes_exec_write) from VALID/INVALID, or by a GET replay
-// from INVALID (hermes_exec_read -> write replay), and its first mutation leaves the key in an
-// absorbing state (WRITE/REPLAY, see absorbing_state). So every element's result is fixed by S_0
-// and by F, its key's first mutating element:
-//   i < F (or no F): the exec function against S_0;  i = F: S_0 -> its shadow;  i > F: against WRITE.
-// Three passes instead of lookup + re-reading every op and entry line:
-//   k_local_pre    the PUTs only (one op header per element, then bucket + log line per PUT):
-//                  every PUT that mutates S_0 offers F and tags its entry's seqlock byte;
-//   k_local_fused  every element: op slab through LDS, bucket, log line (the whole 64-B entry, four
-//                  lanes) -- F is final for every key not INVALID at S_0, so each element resolves
-//                  right there, F applies itself to its shadow, and the slab is written back once;
-//                  elements of INVALID keys (where GET replays may mutate: they offer F here) wait;
-//   k_local_deferred  those waiting elements, against the final F.
-// k_commit then installs the shadows. Measured against k_lookup + k_resolve0: the entry line and
-// the op slab are read once instead of twice.
-// work-skipping timing modes of k_local_pre (tools/dbg_modes.sh): compiled in only with
-// -DHKV_DEBUG_MODES; the default build folds every test to false
-#ifdef HKV_DEBUG_MODES
-#define HKV_DBG_ON(a, bit) (((a).dbg & (bit)) != 0)
-#else
-#define HKV_DBG_ON(a, bit) false
-#endif
-// Round 5: 2048 elements per block (512 threads), a 2048-slot table: each block looks up and offers
-// each of its PUT keys once, so doubling the block removes the second lookup of the keys two 1024-element
-// halves shared, and the two head elements per thread instead of four cut registers. Same box, 3 x 20
-// steps (gpurun_out/r05v): prepass 76.1 -> 64.2 us, 4.25-4.29 -> 4.27-4.36 G ops/s; 1536 (86 us), 4096 (78 us),
-// a 2048-element head (79 us) and a 4096-slot table (111 us) were slower
-constexpr int kPreElems = 2048;            // elements per k_local_pre block
-constexpr int kPreThreads = kPreElems / 4; // four of its own elements per thread
-constexpr int kPreHead = 1024;             // launch head whose PUT keys every block knows
-constexpr int kPreHash = 2048;             // LDS slots of a (key -> first PUT) table (a power of two)
-constexpr int kLfElems = 32;             // elements per k_local_fused block (one wave)
-enum { kCtrDefer = 3 };
-enum : uint8_t { kStDefer = 3 };
-
-// The key (bytes 8..15) and the meta (bytes 16..32) of a log line held 16 B per lane, in every lane
-__device__ __forceinline__ uint64_t line_key_meta(const uint4 &ln, Meta &m)
-{
-    const uint64_t ek = (uint64_t)(uint32_t)__shfl((int)ln.z, 0, 4) | ((uint64_t)(uint32_t)__shfl((int)ln.w, 0, 4) << 32);
-    m.w4 = (uint32_t)__shfl((int)ln.x, 1, 4);
-    m.w5 = (uint32_t)__shfl((int)ln.y, 1, 4);
-    m.ver = (uint32_t)__shfl((int)ln.z, 1, 4);
-    const uint32_t w7 = (uint32_t)__shfl((int)ln.w, 1, 4);
-    const uint32_t b32 = (uint32_t)__shfl((int)ln.x, 2, 4) & 0xFFu;
-    m.llw_cid = (uint8_t)w7;
-    m.llw_ver = (w7 >> 8) | (b32 << 24);
-    return ek;
-}
-
-// element i lies inside its batch's count (launches are under 2^31 elements: 32-bit division,
-// and none at all without counts)
-__device__ __forceinline__ bool in_count(const BatchArgs &a, uint32_t i)
-{
-    if (!a.counts) return true;
-    const uint32_t b = i / (uint32_t)a.stride;
-    return (int32_t)(i - b * (uint32_t)a.stride) < a.counts[b];
-}
-
-// ---- pending header writes (hkv_batch_desc.d_patch, HKV_PATCH_BYTES per element): the second
-// 8-B word of a patch holds opcode (bits 0..7), val_len (8..15), flags (16..31), the value fill
-// byte (32..39), ts reset (40..47) and valid (48..55).
-__device__ __forceinline__ bool patch_valid(uint64_t pb) { return ((pb >> 48) & 0xFFu) != 0; }
-
-// the key of element i as the launch sees it (patched or not)
-__device__ __forceinline__ uint64_t elem_key(const BatchArgs &a, int64_t i)
-{
-    if (a.patch && a.patch[i * 16 + 14]) return *reinterpret_cast<const uint64_t *>(a.patch + i * 16);
-    return *reinterpret_cast<const uint64_t *>(a.elems + i * a.esz);
-}
-
-// a patch applied to the 16-B chunk q (bytes 16q..16q+15) of a 56-B op with a 31-B value
-__device__ __forceinline__ uint4 patch_chunk(uint4 w, int q, uint64_t pa, uint64_t pb)
-{
-    const uint32_t fill = (uint32_t)((pb >> 32) & 0xFFu) * 0x01010101u;
-    const bool vfill = fill != 0, reset = ((pb >> 40) & 0xFFu) != 0;
-    if (q == 0) {
-        w.x = (uint32_t)pa;
-        w.y = (uint32_t)(pa >> 32);
-        // opcode, ST_NEW, val_len; ts.cid (byte 11) and ts.version (12..15) kept unless reset
-        w.z = (uint32_t)(pb & 0xFFu) | ((uint32_t)kNew << 8) | ((uint32_t)((pb >> 8) & 0xFFu) << 16) |
-              (reset ? 0u : (w.z & 0xFF000000u));
-        if (reset) w.w = 0;
-    } else if (q == 1) {
-        const uint32_t flags = (uint32_t)((pb >> 16) & 0xFFFFu);
-        w.x = flags | (vfill ? (fill & 0xFFFF0000u) : (w.x & 0xFFFF0000u));
-        if (vfill) w.y = w.z = w.w = fill;
-    } else if (q == 2) {
-        if (vfill) w.x = w.y = w.z = w.w = fill;
-    } else if (vfill) {  // bytes 48..55: byte 48 is the value's last
-        w.x = (w.x & 0xFFFFFF00u) | (fill & 0xFFu);
-    }
-    return w;
-}
-
 // Every other path: the patches go into the ops first (one thread per element), then the launch
 // runs as usual
 __global__ __launch_bounds__(256) void k_apply_patch(uint8_t *elems, const uint8_t *patch, int64_t n, int32_t esz,
@@ -1528,442 +1189,6 @@ __global__ __launch_bounds__(256) void k_apply_patch(uint8_t *elems, const uint8
         for (uint32_t k = 0; k < st_value; ++k) x[kOpValueOff + k] = fill;
 }
 
-__device__ __forceinline__ uint32_t pre_slot(uint64_t key)
-{
-    return (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - __builtin_ctz(kPreHash))) & (kPreHash - 1);
-}
-
-// (key -> smallest element) in an LDS table of kPreHash slots, key ~0 the empty mark; false when the
-// key cannot go in (key ~0 itself, or a full table)
-__device__ __forceinline__ bool pre_insert(uint64_t *hk, uint32_t *hv, uint64_t key, uint32_t i, bool &created,
-                                           uint32_t &slot)
-{
-    created = false;
-    if (key == ~0ull) return false;
-    uint32_t sl = pre_slot(key);
-    for (int n = 0; n < kPreHash; ++n) {
-        const unsigned long long old = atomicCAS((unsigned long long *)&hk[sl], ~0ull, key);
-        if (old == ~0ull || old == key) {
-            created = old == ~0ull;
-            atomicMin(&hv[sl], i);
-            slot = sl;
-            return true;
-        }
-        sl = (sl + 1) & (kPreHash - 1);
-    }
-    return false;
-}
-
-// a key into an LDS set of kPreHash slots (the head's PUT keys: only membership is asked)
-__device__ __forceinline__ void pre_insert_key(uint64_t *hk, uint64_t key)
-{
-    if (key == ~0ull) return;
-    uint32_t sl = pre_slot(key);
-    for (int n = 0; n < kPreHash; ++n) {
-        const unsigned long long old = atomicCAS((unsigned long long *)&hk[sl], ~0ull, key);
-        if (old == ~0ull || old == key) return;
-        sl = (sl + 1) & (kPreHash - 1);
-    }
-}
-
-// The PUTs of kPreElems elements offer F. Whether a PUT mutates S_0 depends on S_0 alone
-// (hermes_exec_write: VALID or INVALID and no op buffer index), so either every PUT of a key is a
-// candidate or none is, and F is the key's first PUT or nothing. So each block looks up each key
-// once, for its first PUT (an LDS table of the block's PUT keys). A Zipf-hot key's PUTs are spread
-// over every block, and all blocks of the launch are in flight together: every block also reads the
-// keys of the PUTs among the launch's first kPreHead elements (before its own; headers only,
-// L2-resident after the first block) and drops its keys that have a PUT there -- an earlier block
-// offers that one. Four keys per lane group are in flight; the offer is a plain atomicMin.
-constexpr int kPrePair = 4;   // keys per lane group in flight in the prepass's lookups (2 or 8 were slower: DESIGN 6,
-                              // round 5). No occupancy or SGPR attribute: neither moved the prepass
-// No seqlock-byte tags (round 5): k_local_fused loads every hit's F word beside its log line and needs
-// no mark of the keys that have one
-template <int HEAD = kPreHead, bool IL = false>
-__global__ __launch_bounds__(kPreThreads) void k_local_pre(BatchArgs a)
-{
-    __shared__ uint64_t hk[kPreHash], gk[kPreHash];  // the block's PUT keys, the head's
-    __shared__ uint32_t hv[kPreHash];
-    __shared__ uint32_t dl[kPreElems];               // distinct keys: slots of hk, or ~index (no slot)
-    __shared__ uint32_t nd;
-    const int tid = threadIdx.x, q = tid & 3, gbase = (tid & 63) & ~3;
-    if (tid == 0) {
-        nd = 0;
-        if (blockIdx.x == 0) a.ctr[kCtrDefer] = 0;
-    }
-    for (int j = tid; j < kPreHash; j += kPreThreads) {
-        hk[j] = ~0ull;
-        gk[j] = ~0ull;
-        hv[j] = kNone;
-    }
-    if (HKV_DBG_ON(a, 8)) return;
-    const int64_t i0 = (int64_t)blockIdx.x * kPreElems;
-    const int64_t head_end = HKV_DBG_ON(a, 4) ? 0 : i0 < HEAD ? i0 : HEAD;  // the head: elements before the block's own
-    // PUTs that are not skipped (hermes_skip_op, hermesKV.c:709-769). Reading every op header is a
-    // pass over the whole op slab; with the caller's opcode mirror only the PUTs' headers are read
-    // (the others read element 0's, one cached line; k_local_fused checks the mirror against every
-    // element's opcode). Loads are unconditional and all issued before the first is used.
-    constexpr int kOwnK = kPreElems / kPreThreads, kAllK = kOwnK + (HEAD + kPreThreads - 1) / kPreThreads;
-    U64x2 h[kAllK];
-    bool in[kAllK];
-    uint8_t opm[kAllK];
-    U64x2 pt[kAllK];
-#pragma unroll
-    for (int k = 0; k < kAllK; ++k) {
-        const bool own = k < kOwnK;
-        const int64_t i = own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid;
-        in[k] = i < a.n && (own || i < head_end);
-        opm[k] = a.opc ? a.opc[in[k] ? i : 0] : (uint8_t)kOpPut;
-    }
-    if (a.patch) {
-        // the patches first: a refilled PUT's patch holds all the prepass needs (key, opcode, ST_NEW),
-        // so only the PUTs kept from the last round read their op header (a second dependent load
-        // for them, against a third of the op slab's lines fetched for nothing)
-#pragma unroll
-        for (int k = 0; k < kAllK; ++k) {
-            const bool own = k < kOwnK;
-            const int64_t i = own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid;
-            pt[k] = in[k] && opm[k] == kOpPut ? *reinterpret_cast<const U64x2 *>(a.patch + i * 16) : U64x2{0, 0};
-        }
-#pragma unroll
-        for (int k = 0; k < kAllK; ++k) {
-            const bool own = k < kOwnK;
-            const int64_t i = own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid;
-            h[k] = *reinterpret_cast<const U64x2 *>(a.elems + (in[k] && opm[k] == kOpPut && !patch_valid(pt[k].b) ? i : 0) * 56);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kAllK; ++k) {
-            const bool own = k < kOwnK;
-            const int64_t i = own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid;
-            h[k] = *reinterpret_cast<const U64x2 *>(a.elems + (in[k] && opm[k] == kOpPut ? i : 0) * 56);
-            pt[k] = U64x2{0, 0};
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < kAllK; ++k)
-        if (patch_valid(pt[k].b)) {   // a patched element: its key and opcode, state ST_NEW
-            h[k].a = pt[k].a;
-            h[k].b = (h[k].b & ~0xFFFFull) | (pt[k].b & 0xFFu) | ((uint64_t)kNew << 8);
-        }
-#pragma unroll
-    for (int k = 0; k < kAllK; ++k) {
-        const bool own = k < kOwnK;
-        const int64_t i = own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid;
-        // a non-PUT read element 0's raw header, which a patch may have made stale: only the
-        // mirror's PUTs take part
-        in[k] = in[k] && opm[k] == kOpPut && in_count(a, (uint32_t)i);
-    }
-    if (HKV_DBG_ON(a, 16)) {
-        uint64_t acc = 0;
-#pragma unroll
-        for (int k = 0; k < kAllK; ++k) acc += h[k].a ^ h[k].b;
-        if (acc == 0x1234567ull) a.ctr[7] = 1;
-        return;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kAllK; ++k) {
-        const bool own = k < kOwnK;
-        const uint32_t i = (uint32_t)(own ? i0 + k * kPreThreads + tid : (int64_t)(k - kOwnK) * kPreThreads + tid);
-        const uint64_t key = h[k].a;
-        if (!(in[k] && (uint8_t)h[k].b == kOpPut && !skip_elem_os(kLocal, kOpPut, (uint8_t)(h[k].b >> 8)))) continue;
-        bool created;
-        uint32_t sl;
-        if (own) {
-            const bool in_table = pre_insert(hk, hv, key, i, created, sl);
-            if (!in_table || created) {  // a key's first arrival lists it (no slot: it offers for itself)
-                dl[atomicAdd(&nd, 1u)] = in_table ? sl : ~i;
-            }
-        } else {
-            pre_insert_key(gk, key);
-        }
-    }
-    __syncthreads();
-    const Ctx c = make_ctx(a);
-    const uint64_t hput[2] = {0, (uint64_t)kOpPut};
-    const uint32_t cnt = HKV_DBG_ON(a, 2) ? 0 : nd;
-    for (uint32_t base = 0; base < cnt; base += (kPreThreads / 4) * kPrePair) {
-        uint64_t key[kPrePair];
-        bool probe[kPrePair], ok[kPrePair];
-        uint32_t idx[kPrePair];
-        uint64_t phys[kPrePair];
-        uint4 ln[kPrePair];
-#pragma unroll
-        for (int k = 0; k < kPrePair; ++k) {
-            const uint32_t j = base + k * (kPreThreads / 4) + (tid >> 2);
-            probe[k] = j < cnt;
-            const uint32_t d = probe[k] ? dl[j] : 0u;
-            idx[k] = !probe[k] ? kNone : d < (uint32_t)kPreHash ? hv[d] : ~d;
-            key[k] = !probe[k] ? 0 : d < (uint32_t)kPreHash ? hk[d] : elem_key(a, (int64_t)idx[k]);
-            if (probe[k] && head_end > 0 && key[k] != ~0ull) {  // a head PUT of the key comes first
-                uint32_t sl = pre_slot(key[k]);
-                for (int n = 0; n < kPreHash; ++n) {
-                    const uint64_t g = gk[sl];
-                    if (g == ~0ull) break;
-                    if (g == key[k]) {
-                        probe[k] = false;
-                        break;
-                    }
-                    sl = (sl + 1) & (kPreHash - 1);
-                }
-            }
-        }
-        lookup_pair<kPrePair, IL>(a, key, probe, q, gbase, ok, phys, ln);
-#pragma unroll
-        for (int k = 0; k < kPrePair; ++k) {
-            Meta m0;
-            const uint64_t ek = line_key_meta(ln[k], m0);
-            if (q != 0 || !ok[k] || ek != key[k]) continue;
-            if (!would_mutate(kLocal, reinterpret_cast<const uint8_t *>(hput), m0, c) || HKV_DBG_ON(a, 1)) continue;
-            atomicMin(a.fw + fw_index(a, phys[k]), ((unsigned long long)(~a.rtag0) << 32) | idx[k]);
-        }
-    }
-}
-
-// exec_read / exec_write (hermesKV.c:251-356, with the skew optimisations of :196-238) for a local op
-// of the direct path (RMWs off) that leaves its key's meta m as it is: the caller has excluded the
-// branches that change it (update_actions, write replays) -- the element is not its key's first
-// mutating element, so would_mutate is false against S_0, or m is the key's meta after that first write
-// -- and only the element's own bytes move, without the generic dispatch's meta updates. An element
-// that would mutate after all raises error flag bit 0, as the generic path's meta check does.
-__device__ __forceinline__ void local_resolve_nm(const BatchArgs &a, uint8_t *x, const uint8_t *ent, const Meta &m)
-{
-    const uint8_t oc = x[8], st = m_state(m);
-    const bool obi_empty = m_obi(m) == kObiEmpty;
-    bool mut = false;
-    if (oc == kOpGet) {
-        if (st == kValid) {
-            copy_value<31>(x + kOpValueOff, ent + kEntryValueOff, 31);
-            x[9] = kGetComplete;
-            x[10] = (uint8_t)((m_val_len(m) >> a.g.shift) - kOpMetaSize);
-        } else if (st == kInvalidWrite || st == kWrite || st == kReplay) {
-            x[9] = kGetStall;
-        } else {
-            x[9] = kEmpty;
-            if (st == kInvalid) {   // hermes_check_membership_n_write_replay_actions, hermesKV.c:179-194
-                const uint8_t lw = m_lwid(m);
-                if (lw < 8 && ((a.g_membership >> lw) & 1u)) x[9] = kGetStall;
-                else mut = obi_empty;
-            }
-        }
-        if (a.g.skew & kSkewReadComplete) hot_read_complete(x, m.ver, m_cid(m));
-    } else if (oc == kOpPut) {
-        mut = (st == kValid || st == kInvalid) && obi_empty;
-        x[9] = kPutStall;
-        if (a.g.skew & kSkewWriteCoalesce) {   // as exec_write (hkv_exec.h)
-            const uint32_t cv = m.ver & 0xFFFFu;
-            uint32_t over = ld32(x + 12);
-            if (st != kReplay && over == 0) {
-                st32(x + 12, cv);
-                over = cv;
-            }
-            if (over > 0 && over + 1u < cv) x[9] = kPutComplete;
-        }
-    }
-    if (mut && a.error_flags) atomicOr(a.error_flags, 1u);
-}
-
-// F of the direct path: S_0 -> S_1 by the exec function on the element's own LDS copies of op (x) and entry
-// (ent, meta m) -- each element has a private copy of its entry, so the image nobody else reads becomes the
-// shadow's bytes, which the caller stores to shadow_of(a, i) whole (apply_to_shadow's result without its
-// byte accesses to global memory)
-__device__ __forceinline__ void local_first_lds(const BatchArgs &a, uint8_t *x, uint32_t i, uint8_t *ent, Meta m)
-{
-    Ctx c = make_ctx(a);
-    // the element's index in its batch (elem_at's, under 2^31 elements: 32-bit division)
-    const uint8_t idx = (uint8_t)(i - i / (uint32_t)a.stride * (uint32_t)a.stride);
-    if (x[8] == kOpGet) exec_read<31>(x, ent, idx, m, c);
-    else if (x[8] == kOpPut) exec_write<31>(x, ent, idx, m, c);
-    meta_store(ent, m);
-}
-
-// Every element, F final (except on INVALID keys): see the section comment. The lookup runs four
-// lanes per element (each lane holds 16 B of the op and of the log line); the LDS copies of op and
-// entry are then resolved one element per lane (see NW below); the ops go back whole.
-// Every hit's F word is loaded beside its log line; the word alone says whether this launch's prepass
-// offered a first candidate for the key (first_cand)
-// SGPR budget of k_local_fused, 80 (round 6: local launch 353-355 -> 341-351 us, 7 -> 8 waves per SIMD): waves are admitted
-// per SIMD by ~800 SGPRs / (ceil(sgpr/16) * 16 + 16) (MI355X_MICROARCH.md, "Residency"), so 92 SGPRs allow
-// 7 waves and 80 allow 8
-// NW waves per block (round 6): each wave loads, looks up and stages its own 32 elements, and after the block's
-// barrier the stage bytes and the state mirror of all NW * 32 elements go out as whole 64-byte blocks (a
-// wave's 32 bytes alone are half a block, which HBM writes with a read-modify-write: tools/calib_bench.hip,
-// 16-B random writes 2.4x the time of 64-B ones).
-// The resolve runs on full waves: between the barriers wave 0 resolves all 64 elements of the block, one per
-// lane, so the divergent exec code is issued once per 64 elements and not once per 32 on half-empty waves. A
-// key's first writer runs its exec function on its LDS copy of the entry (local_first_lds) and the wave then
-// stores the finished images to their shadows, 16 B per lane ("The fused pass's instructions").
-constexpr int kLfWaves = 2;   // waves per k_local_fused block
-template <int P, int NW, bool IL = false>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_sgpr(80))) void k_local_fused(BatchArgs a)
-{
-    constexpr int E = 16 * P;   // elements per wave: P per lane group
-    constexpr int EB = E * NW;  // elements per block
-    static_assert(EB == 64, "one wave resolves the block, one element per lane");
-    // per block element, each wave staging its own E
-    __shared__ uint4 sops_b[EB * 4];      // 64 B per op (56 used)
-    __shared__ uint4 sln_b[EB * 4];
-    __shared__ unsigned long long sfw_b[EB];
-    __shared__ uint32_t sent_b[EB];       // entry id of a hit, kNone otherwise
-    __shared__ uint8_t sprb_b[EB];        // probed (not skipped)
-    __shared__ uint8_t sfl[EB];           // the block's first writers (F), whose images go to their shadows
-    __shared__ uint32_t sst[EB / 4], sstate[EB / 4];   // the block's stage bytes and state mirror
-    __shared__ uint32_t sdef[EB];
-    __shared__ uint32_t ndef;
-    const int w = threadIdx.x >> 6, tid = threadIdx.x & 63, q = tid & 3, gbase = tid & ~3;
-    uint4 *sops = sops_b + w * E * 4, *sln = sln_b + w * E * 4;
-    unsigned long long *sfw = sfw_b + w * E;
-    uint32_t *sent = sent_b + w * E;
-    uint8_t *sprb = sprb_b + w * E;
-    const int64_t ib = (int64_t)blockIdx.x * EB, i0 = ib + (int64_t)w * E;
-    if (threadIdx.x == 0) ndef = 0;
-    uint64_t key[P];
-    bool probe[P], ok[P], live[P];
-    uint64_t phys[P];
-    uint4 ln[P], op[P];
-    int te[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        te[k] = k * 16 + (tid >> 2);
-        const int64_t i = i0 + te[k];
-        live[k] = i < a.n;
-        op[k] = make_uint4(0u, 0u, 0u, 0u);
-        if (live[k]) {
-            const uint8_t *xg = a.elems + i * 56 + 16 * q;
-            U64x2 p{0, 0};
-            if (a.patch) p = *reinterpret_cast<const U64x2 *>(a.patch + i * 16);
-            if (q < 3) {
-                op[k] = *reinterpret_cast<const uint4 *>(xg);
-            } else {
-                const uint64_t t = *reinterpret_cast<const uint64_t *>(xg);
-                op[k].x = (uint32_t)t;
-                op[k].y = (uint32_t)(t >> 32);
-            }
-            if (patch_valid(p.b)) op[k] = patch_chunk(op[k], q, p.a, p.b);
-        }
-        sops[te[k] * 4 + q] = op[k];
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        // lane 0 of the group holds op bytes 0..15: the key and the header
-        key[k] = (uint64_t)(uint32_t)__shfl((int)op[k].x, 0, 4) | ((uint64_t)(uint32_t)__shfl((int)op[k].y, 0, 4) << 32);
-        const uint32_t h0 = (uint32_t)__shfl((int)op[k].z, 0, 4);
-        probe[k] = false;
-        if (live[k] && !HKV_DBG_ON(a, 128))
-            probe[k] = in_count(a, (uint32_t)(i0 + te[k])) && !skip_elem_os(kLocal, (uint8_t)h0, (uint8_t)(h0 >> 8));
-    }
-    unsigned long long fwv[P];   // a hit's F word, loaded beside its log line
-    bool inl[P];                 // (IL) the hit is its bucket's inline key
-    if (HKV_DBG_ON(a, 512)) {   // (timing modes) no F loads
-        lookup_pair<P, IL>(a, key, probe, q, gbase, ok, phys, ln, nullptr, inl);
-#pragma unroll
-        for (int k = 0; k < P; ++k) fwv[k] = ~0ull;
-    } else {
-        lookup_pair_f<P, IL>(a, key, probe, q, gbase, ok, phys, ln, fwv, nullptr, inl);
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        Meta m;
-        const uint64_t ek = line_key_meta(ln[k], m);
-        const bool hit = ok[k] && ek == key[k];
-        // keys INVALID at S_0 take their F after this pass (k_local_deferred)
-        const unsigned long long f = hit && m_state(m) != kInvalid && q == 0 ? fwv[k] : ~0ull;
-        if (hit) sln[te[k] * 4 + q] = ln[k];
-        if (q == 0) {
-            sfw[te[k]] = f;
-            sent[te[k]] = hit ? (uint32_t)(phys[k] / a.g.entry_unit) | (IL && inl[k] ? kEntInline : 0u) : kNone;
-            sprb[te[k]] = probe[k];
-        }
-    }
-    __syncthreads();
-    // wave 0 resolves the block's EB elements, one per lane, on both waves' LDS copies: the exec code's
-    // branches are issued once per 64 elements; wave 1 waits at the barrier
-    if (__builtin_amdgcn_readfirstlane(w) == 0 && !HKV_DBG_ON(a, 64)) {
-        const int64_t i = ib + tid;
-        uint8_t st = kStDone;
-        if (i < a.n) {
-            uint8_t *x = reinterpret_cast<uint8_t *>(&sops_b[tid * 4]);
-            uint8_t *ent = reinterpret_cast<uint8_t *>(&sln_b[tid * 4]);
-            const uint32_t e = sent_b[tid];
-            const bool prb = sprb_b[tid] != 0;
-            if (e != kNone) {
-                Meta m;
-                meta_load(ent, m);
-                Ctx c = make_ctx(a);
-                const bool wm = would_mutate(kLocal, x, m, c);
-                if (m_state(m) == kInvalid) {
-                    // GET replays may mutate: they offer F now, and the key's elements resolve later
-                    if (wm) {
-                        const uint64_t ph = phys_of(a, ent_id<IL>(e));
-                        offer(a.fw + fw_index(a, ph), a.rtag0, (uint32_t)i);
-                        if ((uint8_t)(m.w5 >> 16) != a.ltag)
-                            entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(x))[kEntryMetaOff + 4] = a.ltag;
-                    }
-                    st = kStDefer;
-                    sdef[atomicAdd(&ndef, 1u)] = (uint32_t)i;
-                } else {
-                    const uint32_t f = first_cand(sfw_b[tid], a.rtag0);
-                    // a mutating element must have offered itself in k_local_pre
-                    if (wm && (f == kNone || f > (uint32_t)i) && a.error_flags) atomicOr(a.error_flags, 4u);
-                    if ((uint32_t)i == f) {
-                        local_first_lds(a, x, (uint32_t)i, ent, m);
-                        st = kStCommit;
-                    } else {
-                        // F of a key that is not INVALID is its first PUT (k_local_pre)
-                        local_resolve_nm(a, x, ent, f != kNone && (uint32_t)i > f ? after_first<kLocal>(a, m, f, 1) : m);
-                    }
-                }
-            } else if (prb) {
-                x[9] = kMiss;
-            }
-            // k_local_pre read only the PUTs the caller's opcode mirror names
-            if (a.opc && prb && x[8] == kOpPut && a.opc[i] != kOpPut && a.error_flags) atomicOr(a.error_flags, 8u);
-            if (!HKV_DBG_ON(a, 1024)) a.ent[i] = e;
-            // a deferred element's state byte is written again by k_local_deferred, after this pass
-            reinterpret_cast<uint8_t *>(sst)[tid] = st;
-            reinterpret_cast<uint8_t *>(sstate)[tid] = x[9];
-        }
-        // the first writers' entry images, finished in LDS, go to their shadows: four lanes per image, 16 B
-        // each, 16 images per step
-        const unsigned long long fm = __ballot(st == kStCommit);
-        if (fm && !HKV_DBG_ON(a, 1024)) {
-            if (st == kStCommit) sfl[__popcll(fm & ((1ull << tid) - 1ull))] = (uint8_t)tid;
-            __threadfence_block();   // the images and the list, written by this wave's other lanes
-            const int nf = __popcll(fm);
-            for (int j = tid >> 2; j < nf; j += 16) {
-                const int t = sfl[j];
-                reinterpret_cast<uint4 *>(shadow_of(a, (uint32_t)(ib + t)))[q] = sln_b[t * 4 + q];
-            }
-        }
-    }
-    __syncthreads();
-    // the block's stage bytes and state mirror as whole blocks (a partial last block byte by byte)
-    if (!HKV_DBG_ON(a, 1024) && !HKV_DBG_ON(a, 64)) {
-        if (ib + EB <= a.n && ((uintptr_t)a.state_out & 3) == 0) {   // (st is 256-byte aligned)
-            if ((int)threadIdx.x < EB / 4) {
-                reinterpret_cast<uint32_t *>(a.st + ib)[threadIdx.x] = sst[threadIdx.x];
-                if (a.state_out) reinterpret_cast<uint32_t *>(a.state_out + ib)[threadIdx.x] = sstate[threadIdx.x];
-            }
-        } else if ((int)threadIdx.x < EB && ib + threadIdx.x < a.n) {
-            a.st[ib + threadIdx.x] = reinterpret_cast<const uint8_t *>(sst)[threadIdx.x];
-            if (a.state_out) a.state_out[ib + threadIdx.x] = reinterpret_cast<const uint8_t *>(sstate)[threadIdx.x];
-        }
-    }
-    // the waiting elements (keys INVALID at S_0: rare), appended once per block
-    if (ndef && threadIdx.x == 0) {
-        const uint32_t base = atomicAdd(&a.ctr[kCtrDefer], ndef);
-        for (uint32_t j = 0; j < ndef; ++j) a.fbl[base + j] = sdef[j];
-    }
-#pragma unroll
-    for (int k = 0; k < P; ++k) {
-        if (!live[k] || HKV_DBG_ON(a, 256)) continue;
-        uint8_t *xg = a.elems + (i0 + te[k]) * 56 + 16 * q;
-        const uint4 v = sops[te[k] * 4 + q];
-        if (q < 3) *reinterpret_cast<uint4 *>(xg) = v;
-        else *reinterpret_cast<uint64_t *>(xg) = (uint64_t)v.x | ((uint64_t)v.y << 32);
-    }
-}
-
 // ------------------------------------------------------------------ launches with unique keys
 // HKV_BATCH_UNIQUE: no key appears twice among the launch's elements, so every element is its key's
 // only one and sees S_0 in any serial order: after k_lookup's lookup (four lanes per element, two
@@ -1972,9 +1197,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_sgpr(80))) void 
 // launches: a peer's round slab, see hermeskv.h.) With check_unique every element also swaps its
 // index into its key's F word, tagged with the launch; finding the launch's tag there means a
 // second element of the key (error bit 4).
-template <int TYPE, int SV, int P = kLookupPair>
+template <int TYPE, int SV>
 __global__ __launch_bounds__(256) void k_unique(BatchArgs a)
 {
+    constexpr int P = 1;   // elements per lane group (launch_unique_t has the measurements)
     const int q = threadIdx.x & 3;
     const int gbase = (threadIdx.x & 63) & ~3;
     int64_t gi[P];
@@ -2066,9 +1292,10 @@ __device__ __forceinline__ bool chunk_equal(const uint4 &a, const uint4 &b)
     return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
 }
 
-template <int TYPE, int P = kLookupPair, bool IL = false>
+template <int TYPE, bool IL = false>
 __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 {
+    constexpr int P = 1;        // elements per lane group (launch_unique_t has the measurements)
     constexpr int E = 16 * P;   // elements per wave: P per lane group
     __shared__ uint4 sops[E * 4];
     __shared__ uint4 sln[E * 4];
@@ -2196,9 +1423,10 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 // and each element and the entry line are written back where they changed. An ACK's completion finds
 // its read_write_ops once per position (the rows share the batch layout).
 // No SGPR or occupancy attribute: 80 SGPRs and 8 waves per SIMD were within box noise.
-template <int TYPE, int RMAX, int CH, int P = kLookupPair, bool IL = false>
+template <int TYPE, int RMAX, int CH, bool IL = false>
 __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
 {
+    constexpr int P = kLookupPair;
     constexpr int E = 16 * P;   // positions per wave: P per lane group
     // CH: 16-B chunks of an element held in LDS (1 for 16-B ACKs, 4 for 56-B INVs)
     __shared__ uint4 sops[RMAX][E * CH];
@@ -2462,42 +1690,6 @@ __global__ __launch_bounds__(64) void k_unique_big(BatchArgs a)
     }
 }
 
-// Elements of keys that were INVALID at S_0, against their key's final F (k_resolve0_direct's rules)
-template <bool IL = false>
-__global__ __launch_bounds__(256) void k_local_deferred(BatchArgs a)
-{
-    const uint32_t nd = a.ctr[kCtrDefer];
-    for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < nd; j += gridDim.x * 256u) {
-        const uint32_t i = a.fbl[j];
-        const uint32_t e = a.ent[i];
-        uint8_t *xg;
-        uint8_t idx;
-        Ctx c = make_ctx(a);
-        elem_at(a, i, xg, idx, c);
-        // (IL) k_local_fused wrote the op back whole, its patch applied: the key is the element's
-        uint8_t *entry = IL ? entry_home<IL>(a, e, *reinterpret_cast<const uint64_t *>(xg)) : entry_of(a, e);
-        Meta m;
-        meta_load(entry, m);
-        const uint32_t f = first_cand(*fw_of(a, ent_id<IL>(e)), a.rtag0);
-        uint8_t st = kStDone;
-        if (f == kNone || i < f) {
-            Meta tm = m;
-            dispatch<31>(kLocal, xg, entry, idx, tm, c);
-            if (a.error_flags && !meta_equal(tm, m)) atomicOr(a.error_flags, 1u);
-        } else if (i == f) {
-            apply_to_shadow<kLocal, 31>(a, nullptr, i, entry);
-            st = kStCommit;
-        } else {
-            const Meta m1 = after_first<kLocal>(a, m, f, 0);
-            Meta tm = m1;
-            dispatch<31>(kLocal, xg, entry, idx, tm, c);
-            if (a.error_flags && !meta_equal(tm, m1)) atomicOr(a.error_flags, 1u);
-        }
-        a.st[i] = st;
-        note_state(a, i, xg);
-    }
-}
-
 // Round r >= 1 resolve over the pending elements (sparse: direct global access), against S_r in
 // the shadow of round r-1's first candidate of the element's key.
 // After the last round, elements still pending go to the fallback list.
@@ -2582,52 +1774,6 @@ __global__ __launch_bounds__(256) void k_commit(BatchArgs a)
         d4[3] = w3;
     } else {
         copy_entry(dst, src, a.g.entry_size);
-    }
-}
-
-// k_commit for 64-B entries over few commits (the local direct path: one per key a PUT first
-// wrote): each wave takes 1024 elements, reads their stage bytes 16 per lane, lists the committing
-// ones in LDS (a wave-wide prefix sum of the per-lane counts), then copies their shadows 16
-// entries at a time, four lanes per entry. One wave per 1024 elements instead of one thread per
-// element: k_commit's cost was its 4M threads, not its copies.
-constexpr int kCwElems = 1024;
-template <bool IL = false>
-__global__ __launch_bounds__(256) void k_commit_w(BatchArgs a)
-{
-    __shared__ uint32_t lst[4][kCwElems];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t e0 = ((int64_t)blockIdx.x * 4 + w) * kCwElems + 16 * lane;
-    uint32_t m = 0;
-    if (e0 + 16 <= a.n) {   // st is 256-byte aligned and e0 a multiple of 16
-        const uint4 s4 = *reinterpret_cast<const uint4 *>(a.st + e0);
-        const uint32_t sw[4] = {s4.x, s4.y, s4.z, s4.w};
-#pragma unroll
-        for (int b = 0; b < 16; ++b)
-            if (((sw[b >> 2] >> (8 * (b & 3))) & 0xFFu) == kStCommit) m |= 1u << b;
-    } else {
-        for (int b = 0; b < 16; ++b)
-            if (e0 + b < a.n && a.st[e0 + b] == kStCommit) m |= 1u << b;
-    }
-    const uint32_t c = __popc(m);
-    uint32_t incl = c;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t v = (uint32_t)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += v;
-    }
-    const uint32_t total = (uint32_t)__shfl((int)incl, 63, 64);
-    for (uint32_t pos = incl - c; m; m &= m - 1) lst[w][pos++] = (uint32_t)e0 + (uint32_t)(__ffs(m) - 1);
-    __syncthreads();
-    const int q = lane & 3;
-    for (uint32_t j = (uint32_t)(lane >> 2); j < total; j += 16) {
-        const uint32_t i = lst[w][j];
-        const uint4 v = reinterpret_cast<const uint4 *>(shadow_of(a, i))[q];
-        if (IL) {   // the shadow is an entry image: its key (bytes 8..15, lane 0's) names the bucket
-            const uint64_t key = (uint64_t)(uint32_t)__shfl((int)v.z, 0, 4) | ((uint64_t)(uint32_t)__shfl((int)v.w, 0, 4) << 32);
-            reinterpret_cast<uint4 *>(entry_home<IL>(a, a.ent[i], key))[q] = v;
-        } else {
-            reinterpret_cast<uint4 *>(entry_of(a, a.ent[i]))[q] = v;
-        }
     }
 }
 
@@ -3356,18 +2502,13 @@ __global__ void k_node_suspected(const uint8_t *elems, const int32_t *ns_idx, in
 // ------------------------------------------------------------------ host side
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-size_t batch_scratch_bytes(int64_t cap, uint32_t entry_size)
+// The per-launch scratch of cap elements, laid out once: each array 256-byte aligned, in this order from base.
+// Returns the bytes taken.
+static size_t carve(BatchLaunch &bl, uintptr_t base, int64_t cap, uint32_t entry_size)
 {
-    return align256(4 * (size_t)cap) * 3 + align256((size_t)cap) + align256(16 * (size_t)cap) * 2 + 256 +
-           align256(2 * (size_t)cap) +
-           align256((size_t)entry_size * (size_t)cap);
-}
-
-void batch_carve(BatchLaunch &bl, uint8_t *base, int64_t cap, uint32_t entry_size)
-{
-    uint8_t *p = base;
+    uintptr_t p = base;
     auto take = [&](size_t bytes) {
-        uint8_t *r = p;
+        uint8_t *r = reinterpret_cast<uint8_t *>(p);
         p += align256(bytes);
         return r;
     };
@@ -3381,6 +2522,19 @@ void batch_carve(BatchLaunch &bl, uint8_t *base, int64_t cap, uint32_t entry_siz
     bl.hx = reinterpret_cast<uint64_t *>(take(16 * (size_t)cap));
     bl.fk = reinterpret_cast<uint16_t *>(take(2 * (size_t)cap));
     bl.cap = (uint32_t)cap;
+    return (size_t)(p - base);
+}
+
+// the size is the carve from address zero of a launch nobody uses
+size_t batch_scratch_bytes(int64_t cap, uint32_t entry_size)
+{
+    BatchLaunch bl{};
+    return carve(bl, 0, cap, entry_size);
+}
+
+void batch_carve(BatchLaunch &bl, uint8_t *base, int64_t cap, uint32_t entry_size)
+{
+    carve(bl, reinterpret_cast<uintptr_t>(base), cap, entry_size);
 }
 
 size_t batch_fw_words(uint64_t log_cap) { return (size_t)(log_cap >> 6); }
@@ -3465,7 +2619,7 @@ static BatchPlan plan_batch(const BatchLaunch &bl)
     if (!bl.patch) p.patches = Patches::kNone;
     else if (p.engine == Engine::kSmall) p.patches = Patches::kApplyFirst;
     else if (p.engine == Engine::kLocalDirect) p.patches = Patches::kByEngine;
-    else if (type == kLocal && p.big && !bl.offsets && sv != 31 && sv <= 320 && bl.esz % 8 == 0 &&
+    else if (type == kLocal && p.big && !bl.offsets && sv != 31 && sv <= kPirMaxValue && bl.esz % 8 == 0 &&
              (uint32_t)bl.esz >= vend && (uint32_t)bl.esz <= vend + 8)
         p.patches = Patches::kInResolve;
     else p.patches = Patches::kApplyFirst;
@@ -3545,39 +2699,16 @@ static BatchArgs make_args(const BatchLaunch &bl, const BatchPlan &p)
 }
 
 // ---- the engines' launchers; each returns 0 or launch_batch's -3
-// Separate inline instances of the local kernels: a runtime branch in k_local_fused cost a wave of occupancy
-// 
-template <bool IL>
-static void launch_local_il(const BatchArgs &a, hipStream_t s)
-{
-    const int64_t n = a.n;
-    const dim3 pgrid((unsigned)((n + kPreElems - 1) / kPreElems));
-    const dim3 fgrid((unsigned)((n + 32 * kLfWaves - 1) / (32 * kLfWaves)));
-    hipLaunchKernelGGL((k_local_pre<kPreHead, IL>), pgrid, dim3(kPreThreads), 0, s, a);
-    hipLaunchKernelGGL((k_local_fused<2, kLfWaves, IL>), fgrid, dim3(64 * kLfWaves), 0, s, a);
-    // the waiting elements' count is on the device: enough workgroups for the rounds after a
-    // membership change (configs[4]: ~100 K elements of keys a failed peer left INVALID), which
-    // return at once when there are few
-    hipLaunchKernelGGL(k_local_deferred<IL>, dim3(128u), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_commit_w<IL>, dim3((unsigned)((n + 4 * kCwElems - 1) / (4 * kCwElems))), dim3(256), 0, s, a);
-}
-
-static int launch_local(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
-{
-    if (p.il) launch_local_il<true>(a, s);
-    else launch_local_il<false>(a, s);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
 // k_unique_rows: two positions per lane group, 32 per wave
+constexpr int kRowsElems = 16 * kLookupPair;   // positions per k_unique_rows block (its E)
 template <int T, int CH>
 static void launch_rows(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
 {
-    const unsigned lgrid = (unsigned)((a.n + kLfElems - 1) / kLfElems);
+    const unsigned lgrid = (unsigned)((a.n + kRowsElems - 1) / kRowsElems);
     with_bool(p.il, [&](auto il) {
         constexpr bool IL = decltype(il)::value;
-        if (p.rmax == 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        if (p.rmax == 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH, IL>), dim3(lgrid), dim3(64), 0, s, a);
     });
 }
 
@@ -3589,12 +2720,12 @@ static void launch_unique_t(const BatchArgs &a, const BatchPlan &p, hipStream_t 
     if (p.engine == Engine::kUniqueLds64) {
         const unsigned g1 = (unsigned)((a.n + 15) / 16);
         with_bool(p.il, [&](auto il) {
-            hipLaunchKernelGGL((k_unique_lds<T, 1, decltype(il)::value>), dim3(g1), dim3(64), 0, s, a);
+            hipLaunchKernelGGL((k_unique_lds<T, decltype(il)::value>), dim3(g1), dim3(64), 0, s, a);
         });
     } else {
         const unsigned ugrid1 = (unsigned)((a.n + 63) / 64);
         with_sv(p.sv, [&](auto v) {
-            hipLaunchKernelGGL((k_unique<T, decltype(v)::value, 1>), dim3(ugrid1), dim3(256), 0, s, a);
+            hipLaunchKernelGGL((k_unique<T, decltype(v)::value>), dim3(ugrid1), dim3(256), 0, s, a);
         });
     }
 }
@@ -3656,14 +2787,14 @@ static int launch_rounds(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
     const unsigned grid = (unsigned)((n + 255) / 256);
     if (p.engine == Engine::kValsOnePass) {
         with_bool(p.il, [&](auto il) {
-            hipLaunchKernelGGL((k_lookup<1, decltype(il)::value>), dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a,
+            hipLaunchKernelGGL(k_lookup<decltype(il)::value>, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, a,
                                (int64_t)0, n);
         });
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
     const int64_t head = p.lookup_head;
-    hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((head + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, head);
-    if (n > head) hipLaunchKernelGGL(k_lookup<1>, dim3((unsigned)((n - head + 63) / 64)), dim3(256), 0, s, a, head, n);
+    hipLaunchKernelGGL(k_lookup<>, dim3((unsigned)((head + 63) / 64)), dim3(256), 0, s, a, (int64_t)0, head);
+    if (n > head) hipLaunchKernelGGL(k_lookup<>, dim3((unsigned)((n - head + 63) / 64)), dim3(256), 0, s, a, head, n);
     int rc = 0;
     if (p.engine == Engine::kRoundsAckDirect) {
         hipLaunchKernelGGL(k_ack_resolve, dim3(grid), dim3(256), 0, s, a);
