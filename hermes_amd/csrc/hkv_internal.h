@@ -215,6 +215,22 @@ int launch_table_extract(const Geometry &g, const uint8_t *index, const uint8_t 
 // 16-byte aligned and n rounded up to 64 bytes long (a wave stores its 16 records' bytes at once, zero past n).
 int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, uint8_t *line, const uint8_t *records,
                          uint64_t n, unsigned long long *result, hipStream_t s, uint8_t *missed_flag = nullptr);
+// Key-level delta repair (hermeskv.h "Key-level delta repair"), three read-only passes with the residency rule of
+// the ones above (`line` non-NULL: the inline keys are read from their lines). Summaries: launch_table_extract's
+// arguments and counts, with 16-B summaries (at most cap) where it writes records. Need: n summaries looked up and
+// classed into result[0..5] (missed, newer, validate, same, state_only, older), the keys of the first three classes
+// compacted to need_keys (at most need_cap) and counted in result[6]; result[0..7] zeroed first. Fetch: record i =
+// the masked entry image of keys[i], or zero but for the key; result[0..1] (found, absent) zeroed first.
+int launch_table_summaries(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                           uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *summaries, uint64_t cap,
+                           unsigned long long *result, const uint8_t *part_sel, uint32_t part_bits, int device,
+                           hipStream_t s);
+int launch_table_need(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                      const uint8_t *summaries, uint64_t n, unsigned long long *need_keys, uint64_t need_cap,
+                      unsigned long long *result, int device, hipStream_t s);
+int launch_table_fetch(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                       const unsigned long long *keys, uint64_t n, uint8_t *records, unsigned long long *result,
+                       int device, hipStream_t s);
 // The upsert's inserts (hermeskv.h "Upsert", step 2) into index and log, after an install with missed_flag and the
 // host's read of its missed count m (1 <= m <= n <= 2^31 - 1): the scan of the flags into ranks, the missed
 // records' (bucket, rank) pairs, their stable sort by bucket, the per-bucket replay of mica_insert_one, and the

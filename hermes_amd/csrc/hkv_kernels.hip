@@ -1004,6 +1004,296 @@ int launch_table_install(const Geometry &g, const uint8_t *index, uint8_t *log, 
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
+// ------------------------------------------------------------------ key-level delta repair: summaries, need, fetch
+// hermeskv.h "Key-level delta repair". Three read-only passes: the extract's pass that leaves 16 B per key instead
+// of a record, the install's lookup that only classes, and the install's lookup that copies the entry out.
+//
+// k_table_summaries is k_table_extract in its count and reserve parts -- the same loads, the same liveness, mask
+// and min_ts rules, one returning atomic per block and step -- written out again so that the extract's instances
+// stay the code they are. Its write part differs: a summary needs an entry's bytes 8..31 only, so instead of four
+// lanes moving one record together, each lane of the group takes one of the bucket's records (the q-th, then the
+// q+4-th), loads the entry's first 32 B -- one sector, whatever the entry size, which is why there is no BIG
+// instance -- and stores one whole 16-B summary. (Each lane writing the summaries of the two slots whose words it
+// already holds needs no shuffle, but its work follows the slots -- which fill from slot 7 down, so lane 3 does
+// most of it -- and its IL instance takes 133 VGPRs: measured slower at every selection)
+template <bool IL, bool MASKED>
+__global__ __launch_bounds__(kCensusBlock) void k_table_summaries(const uint8_t *__restrict__ index,
+                                                                  const uint8_t *__restrict__ log,
+                                                                  const uint8_t *__restrict__ line, uint64_t bkt_lo,
+                                                                  uint64_t bkt_hi, uint64_t log_mask, uint64_t log_head,
+                                                                  uint64_t log_cap, uint64_t min_ts,
+                                                                  uint4 *__restrict__ summaries, uint64_t cap,
+                                                                  unsigned long long *result,
+                                                                  const uint8_t *__restrict__ part_sel,
+                                                                  uint64_t part_mask_of)
+{
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3, wave = threadIdx.x >> 6;
+    const uint64_t tiles = (bkt_hi - bkt_lo + kExtractBktsPerStep - 1) / kExtractBktsPerStep;
+    __shared__ unsigned long long s_wtot[kCensusBlock / 64], s_base;
+    uint32_t n_scanned[1] = {0};
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // (block-uniform)
+        const uint64_t b0 = bkt_lo + tile * kExtractBktsPerStep + (threadIdx.x >> 2);   // (the four lanes of a group share it)
+        // count: as k_table_extract (bit 8k + j: slot j of bucket k leaves as a summary)
+        uint4 v[kExtractK];
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            v[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (b < bkt_hi && (!MASKED || part_sel[b & part_mask_of]))
+                v[k] = (IL ? line_words(line, b) : bucket_words(index, b))[q];
+        }
+        uint64_t qm = 0;
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
+            uint32_t o = group_slots(slot_in_use(s0) && in_log_window(log_head, log_cap, off_of<IL>(slot_off_raw(s0))),
+                                     slot_in_use(s1) && in_log_window(log_head, log_cap, off_of<IL>(slot_off_raw(s1))), gbase);
+            if (q == 0) n_scanned[0] += __popc(o);
+            if (min_ts) {   // (uniform)
+                uint32_t left = o;
+                while (left) {   // (group-uniform)
+                    const int j = __ffs(left) - 1;
+                    left &= left - 1;
+                    const uint64_t off = slot_off_raw(group_slot_word(s0, s1, j));
+                    const uint4 m = off_is_inline<IL>(off)
+                                        ? reinterpret_cast<const uint4 *>(line + b * kLineBytes + kLineEntryOff)[1]
+                                        : reinterpret_cast<const uint4 *>(log + (off_of<IL>(off) & log_mask))[1];
+                    if ((((uint64_t)m.z << 8) | (m.y >> 24)) < min_ts) o &= ~(1u << j);
+                }
+            }
+            qm |= (uint64_t)o << (8 * k);
+        }
+        // reserve: as k_table_extract, one returning atomic on the counter per block and step
+        const uint32_t cnt = (uint32_t)__popcll(qm);
+        uint32_t x = q == 0 ? cnt : 0u;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d);
+            if (lane >= d) x += y;
+        }
+        const uint32_t excl = (uint32_t)__shfl(x, 0, 4) - cnt;
+        const uint32_t wtot = (uint32_t)__shfl(x, 63);
+        if (lane == 0) s_wtot[wave] = wtot;
+        __syncthreads();
+        uint64_t before = excl, total = 0;
+#pragma unroll
+        for (int w = 0; w < kCensusBlock / 64; ++w) {
+            const uint64_t t = s_wtot[w];
+            if (w < wave) before += t;
+            total += t;
+        }
+        if (threadIdx.x == 0) s_base = total ? atomicAdd(&result[0], (unsigned long long)total) : 0ull;
+        __syncthreads();
+        uint64_t pos = s_base + before;   // (group-uniform) this group's first summary
+        // write: lane q takes the bucket's q-th record, then its q+4-th
+#pragma unroll
+        for (int k = 0; k < kExtractK; ++k) {
+            const uint64_t b = b0 + (uint64_t)k * kCensusBktsPerBlock;
+            const uint64_t s0 = u64_of(v[k].x, v[k].y), s1 = u64_of(v[k].z, v[k].w);
+            const uint32_t m8 = (uint32_t)(qm >> (8 * k)) & 0xFFu, nk = __popc(m8);
+            for (uint32_t r = 0; r < nk; r += 4) {   // (group-uniform)
+                uint32_t m = m8;
+#pragma unroll
+                for (uint32_t t = 0; t < 7; ++t)
+                    if (t < r + q) m &= m - 1;   // drop the records before mine
+                const int j = m ? __ffs(m) - 1 : 0;
+                // slot j's word lives in lane j >> 1 (j differs per lane here, so both of that lane's words travel)
+                const uint64_t w0 = __shfl(s0, j >> 1, 4), w1 = __shfl(s1, j >> 1, 4);
+                const uint64_t off = slot_off_raw((j & 1) ? w1 : w0);
+                if (m && pos + r + q < cap) {
+                    const uint4 *ent = off_is_inline<IL>(off)
+                                           ? reinterpret_cast<const uint4 *>(line + b * kLineBytes + kLineEntryOff)
+                                           : reinterpret_cast<const uint4 *>(log + (off_of<IL>(off) & log_mask));
+                    const uint4 e0 = ent[0], e1 = ent[1];   // bytes 8..15: the key; 18 state, 23 ts cid, 24..27 ts version
+                    summaries[pos + r + q] = make_uint4(e0.z, e0.w, e1.z, (e1.y >> 24) | (((e1.x >> 16) & 0xFFu) << 8));
+                }
+            }
+            pos += nk;
+        }
+    }
+    block_reduce(n_scanned, result + 1);
+}
+
+// word indices of hkv_need_result
+enum : uint32_t { kNdMissed = 0, kNdNewer = 1, kNdValidate = 2, kNdSame = 3, kNdStateOnly = 4, kNdOlder = 5, kNdNeeded = 6 };
+
+// One summary per group of four lanes: the install's lookup (group_probe, then the 8-byte key compare on the
+// entry's first 16 B), and lane 1, which holds the entry's bytes 16..31, classes the summary against them. Only
+// the entry's first 32 B are read, so one instance serves every entry size. The six counts stay in registers
+// until the block's end; the needed keys are compacted with the extract's reservation -- a ballot per wave, the
+// waves' totals through LDS, ONE returning atomic on result[kNdNeeded] per block and step.
+template <bool IL>
+__global__ __launch_bounds__(kCensusBlock) void k_table_need(const uint8_t *__restrict__ index,
+                                                             const uint8_t *__restrict__ log,
+                                                             const uint8_t *__restrict__ line,
+                                                             const uint4 *__restrict__ summaries, uint64_t n,
+                                                             uint64_t bkt_mask, uint64_t log_mask, uint64_t log_head,
+                                                             uint64_t log_cap, unsigned long long *__restrict__ need_keys,
+                                                             uint64_t need_cap, unsigned long long *result)
+{
+    Geometry g{};   // (the fields the probe reads)
+    g.bkt_mask = bkt_mask, g.log_mask = log_mask, g.log_head = log_head, g.log_cap = log_cap;
+    const int q = threadIdx.x & 3, lane = threadIdx.x & 63, gbase = lane & ~3, wave = threadIdx.x >> 6;
+    __shared__ unsigned long long s_wtot[kCensusBlock / 64], s_base;
+    uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};   // lane 1 of a group counts for it
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kCensusBktsPerBlock; i0 < n;
+         i0 += (uint64_t)gridDim.x * kCensusBktsPerBlock) {   // (block-uniform)
+        const uint64_t i = i0 + (threadIdx.x >> 2);
+        const bool live = i < n;   // (the four lanes of a group share i)
+        uint4 sm = make_uint4(0u, 0u, 0u, 0u);
+        if (live) sm = summaries[i];
+        const uint64_t key = u64_of(sm.x, sm.y);
+        const uint64_t bkt = bucket_of(g, key);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u), ev = v;
+        if (live) {
+            const uint4 *src = IL ? line_words(line, bkt) : bucket_words(index, bkt);
+            v = src[q];
+            if (IL && q < 2) ev = src[4 + q];
+        }
+        bool ok, il;
+        uint64_t phys;
+        group_probe<IL>(u64_of(v.x, v.y), u64_of(v.z, v.w), key, live, gbase, g, ok, phys, il);
+        const uint4 *home = reinterpret_cast<const uint4 *>(il ? line_entry_of_bucket(line, bkt) : log + phys);
+        uint4 ln = make_uint4(0u, 0u, 0u, 0u);
+        if (ok && q < 2) ln = il ? ev : home[q];   // lane 0: the key; lane 1: bytes 16..31
+        const bool hit = ok && __shfl(u64_of(ln.z, ln.w), 0, 4) == key;
+        uint32_t cls = kNdMissed;
+        if (hit) {   // (lane 1's is the group's)
+            const uint32_t st = (ln.x >> 16) & 0xFFu, s_st = (sm.w >> 8) & 0xFFu;
+            const uint64_t cur = ((uint64_t)ln.z << 8) | (ln.y >> 24), its = ((uint64_t)sm.z << 8) | (sm.w & 0xFFu);
+            cls = its > cur ? kNdNewer : its < cur ? kNdOlder : s_st == st ? kNdSame : s_st == kValid ? kNdValidate : kNdStateOnly;
+        }
+        const bool mine = q == 1 && live, need = mine && cls <= kNdValidate;
+#pragma unroll
+        for (uint32_t k = 0; k < 6; ++k) cnt[k] += mine && cls == k;
+        const unsigned long long bm = __ballot(need);
+        if (lane == 0) s_wtot[wave] = (unsigned long long)__popcll(bm);
+        __syncthreads();
+        uint64_t before = (uint64_t)__popcll(bm & ((1ull << lane) - 1)), total = 0;
+#pragma unroll
+        for (int w = 0; w < kCensusBlock / 64; ++w) {
+            const uint64_t t = s_wtot[w];
+            if (w < wave) before += t;
+            total += t;
+        }
+        if (threadIdx.x == 0) s_base = total ? atomicAdd(&result[kNdNeeded], (unsigned long long)total) : 0ull;
+        __syncthreads();
+        if (need && s_base + before < need_cap) need_keys[s_base + before] = key;
+    }
+    block_reduce(cnt, result);
+}
+
+// One key per group of four lanes, record i to records[i]: the install's lookup, then the entry leaves as the
+// extract writes a record -- whole 64-B runs, 16 B per lane, the digest's mask applied in registers, a 320-B
+// entry's further runs 64 consecutive bytes per group and instruction, four at a time with their loads before
+// their stores. A key the table does not hold leaves a zero record with its key in bytes 8..15.
+template <bool IL, bool BIG>
+__global__ __launch_bounds__(kCensusBlock) void k_table_fetch(const uint8_t *__restrict__ index,
+                                                              const uint8_t *__restrict__ log,
+                                                              const uint8_t *__restrict__ line,
+                                                              const unsigned long long *__restrict__ keys, uint64_t n,
+                                                              uint64_t bkt_mask, uint64_t log_mask, uint64_t log_head,
+                                                              uint64_t log_cap, uint32_t chunks,
+                                                              uint4 *__restrict__ records, unsigned long long *result)
+{
+    Geometry g{};   // (the fields the probe reads)
+    g.bkt_mask = bkt_mask, g.log_mask = log_mask, g.log_head = log_head, g.log_cap = log_cap;
+    const uint64_t E4 = BIG ? 4ull * chunks : 4ull;   // 16-B chunks of a record
+    const int q = threadIdx.x & 3, gbase = (threadIdx.x & 63) & ~3;
+    const uint64_t mask_a = digest_mask_a(q), mask_b = digest_mask_b(q);
+    uint32_t cnt[2] = {0, 0};   // found, absent: lane 1 of a group counts for it
+    for (uint64_t i0 = (uint64_t)blockIdx.x * kCensusBktsPerBlock; i0 < n;
+         i0 += (uint64_t)gridDim.x * kCensusBktsPerBlock) {   // (block-uniform)
+        const uint64_t i = i0 + (threadIdx.x >> 2);
+        const bool live = i < n;   // (the four lanes of a group share i)
+        const uint64_t key = live ? keys[i] : 0ull;
+        const uint64_t bkt = bucket_of(g, key);
+        uint4 v = make_uint4(0u, 0u, 0u, 0u), ev = v;
+        if (live) {
+            const uint4 *src = IL ? line_words(line, bkt) : bucket_words(index, bkt);
+            v = src[q];
+            if (IL) ev = src[4 + q];
+        }
+        bool ok, il;
+        uint64_t phys;
+        group_probe<IL>(u64_of(v.x, v.y), u64_of(v.z, v.w), key, live, gbase, g, ok, phys, il);
+        const uint4 *home = reinterpret_cast<const uint4 *>(il ? line_entry_of_bucket(line, bkt) : log + phys);
+        uint4 c = make_uint4(0u, 0u, 0u, 0u);
+        if (ok) c = il ? ev : home[q];
+        const bool hit = ok && __shfl(u64_of(c.z, c.w), 0, 4) == key;
+        const uint64_t wa = hit ? u64_of(c.x, c.y) & mask_a : 0ull;
+        const uint64_t wb = hit ? u64_of(c.z, c.w) & mask_b : q == 0 ? key : 0ull;
+        uint4 *dst = records + i * E4;
+        if (live) dst[q] = make_uint4((uint32_t)wa, (uint32_t)(wa >> 32), (uint32_t)wb, (uint32_t)(wb >> 32));
+        if (BIG && live) {
+            for (uint32_t k0 = 1; k0 < chunks; k0 += 4) {
+                uint4 t[4];
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    t[k] = hit && k0 + k < chunks ? home[4 * (k0 + k) + q] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+                for (uint32_t k = 0; k < 4; ++k)
+                    if (k0 + k < chunks) dst[4 * (k0 + k) + q] = t[k];
+            }
+        }
+        cnt[0] += q == 1 && live && hit;
+        cnt[1] += q == 1 && live && !hit;
+    }
+    block_reduce(cnt, result);
+}
+
+int launch_table_summaries(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                           uint64_t bkt_lo, uint64_t bkt_hi, uint64_t min_ts, uint8_t *summaries, uint64_t cap,
+                           unsigned long long *result, const uint8_t *part_sel, uint32_t part_bits, int device,
+                           hipStream_t s)
+{
+    if (g.entry_size % 64 || (line && g.entry_size != 64) || bkt_lo > bkt_hi) return -1;
+    if (hipMemsetAsync(result, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    if (bkt_lo == bkt_hi) return 0;
+    const uint64_t part_mask_of = (1ull << part_bits) - 1;
+    const auto launch = [&](auto k) {
+        const dim3 grid = persistent_grid((const void *)k, bkt_hi - bkt_lo, kExtractBktsPerStep, device, 8);
+        hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, bkt_lo, bkt_hi, g.log_mask, g.log_head, g.log_cap, min_ts,
+                           reinterpret_cast<uint4 *>(summaries), cap, result, part_sel, part_mask_of);
+    };
+    if (line) part_sel ? launch(k_table_summaries<true, true>) : launch(k_table_summaries<true, false>);
+    else part_sel ? launch(k_table_summaries<false, true>) : launch(k_table_summaries<false, false>);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_table_need(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                      const uint8_t *summaries, uint64_t n, unsigned long long *need_keys, uint64_t need_cap,
+                      unsigned long long *result, int device, hipStream_t s)
+{
+    if (g.entry_size % 64 || (line && g.entry_size != 64)) return -1;
+    if (hipMemsetAsync(result, 0, 8 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    if (!n) return 0;
+    const dim3 grid = persistent_grid(nullptr, n, kCensusBktsPerBlock, device, 8);
+    const auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, grid, dim3(kCensusBlock), 0, s, index, log, line, reinterpret_cast<const uint4 *>(summaries), n, g.bkt_mask, g.log_mask,
+                           g.log_head, g.log_cap, need_keys, need_cap, result);
+    };
+    line ? launch(k_table_need<true>) : launch(k_table_need<false>);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+int launch_table_fetch(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
+                       const unsigned long long *keys, uint64_t n, uint8_t *records, unsigned long long *result,
+                       int device, hipStream_t s)
+{
+    const uint32_t chunks = g.entry_size / 64;
+    if (g.entry_size % 64 || (line && chunks > 1)) return -1;
+    if (hipMemsetAsync(result, 0, 2 * sizeof(unsigned long long), s) != hipSuccess) return -2;
+    if (!n) return 0;
+    const dim3 grid = persistent_grid(nullptr, n, kCensusBktsPerBlock, device, 8);
+    with_instance(line != nullptr, chunks > 1, [&](auto il, auto big) {
+        hipLaunchKernelGGL((k_table_fetch<decltype(il)::value, decltype(big)::value>), grid, dim3(kCensusBlock), 0, s, index, log, line, keys, n,
+                           g.bkt_mask, g.log_mask, g.log_head, g.log_cap, chunks, reinterpret_cast<uint4 *>(records), result);
+    });
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 // ------------------------------------------------------------------ upsert: the inserts
 // hermeskv.h "Upsert", step 2, after the install with FLAGS has marked the missed records and the host has read
 // their number m. Rank: an exclusive scan of the flags gives each missed record its place among them in record

@@ -1036,6 +1036,66 @@ int hkv_table_extract_parts_async(hkv_table *t, uint32_t part_bits, const uint8_
     });
 }
 
+// Key-level delta repair (hermeskv.h): three read-only passes under the census's rules, through table_pass.
+static_assert(sizeof(hkv_key_summary) == 16 && sizeof(hkv_need_result) == 64 && sizeof(hkv_fetch_result) == 16,
+              "the kernels' word indices");
+uint32_t hkv_key_summary_bytes(void) { return (uint32_t)sizeof(hkv_key_summary); }
+uint32_t hkv_need_result_bytes(void) { return (uint32_t)sizeof(hkv_need_result); }
+uint32_t hkv_fetch_result_bytes(void) { return (uint32_t)sizeof(hkv_fetch_result); }
+
+// the refusals need and fetch share, before anything is launched: `in` holds n items, `out` out_n
+static int key_pass_enter(hkv_table *t, const void *in, uint64_t n, const void *out, uint64_t out_n,
+                          const void *d_result, const char *what)
+{
+    if (!t || !d_result) return fail(-1, "%s: null argument", what);
+    if (t->cfg.rmw_enabled) return fail(-2, "%s: the table has RMWs enabled (a record carries no RMW flag)", what);
+    if ((n && !in) || (out_n && !out)) return fail(-1, "%s: a count without its buffer", what);
+    if (((uintptr_t)in | (uintptr_t)out | (uintptr_t)d_result) & 15)
+        return fail(-1, "%s: the buffers and d_result must be 16-byte aligned", what);
+    return 0;
+}
+
+int hkv_table_summaries_async(hkv_table *t, uint32_t part_bits, const uint8_t *d_part_mask, uint64_t bkt_lo,
+                              uint64_t bkt_hi, uint64_t min_ts, void *d_summaries, uint64_t cap,
+                              hkv_extract_result *d_result, void *stream)
+{
+    if (int rc = extract_enter(t, bkt_lo, bkt_hi, d_summaries, cap, d_result, "summaries")) return rc;
+    if (int rc = part_bits_ok(t, part_bits, "summaries")) return rc;
+    PASS_DETAIL(d, " part_bits %u%s [%llu, %llu)", part_bits, d_part_mask ? "" : " (every partition)",
+                (unsigned long long)bkt_lo, (unsigned long long)bkt_hi);
+    return table_pass(t, stream, "summaries", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_summaries(t->geo, t->d_index, t->d_log, line, bkt_lo, bkt_hi, min_ts,
+                                      static_cast<uint8_t *>(d_summaries), cap,
+                                      reinterpret_cast<unsigned long long *>(d_result), d_part_mask, part_bits,
+                                      t->cfg.device, s);
+    });
+}
+
+int hkv_table_need_async(hkv_table *t, const void *d_summaries, uint64_t n, uint64_t *d_need_keys, uint64_t need_cap,
+                         hkv_need_result *d_result, void *stream)
+{
+    if (int rc = key_pass_enter(t, d_summaries, n, d_need_keys, need_cap, d_result, "need")) return rc;
+    PASS_DETAIL(d, " %llu summaries", (unsigned long long)n);
+    return table_pass(t, stream, "need", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_need(t->geo, t->d_index, t->d_log, line, static_cast<const uint8_t *>(d_summaries), n,
+                                 reinterpret_cast<unsigned long long *>(d_need_keys), need_cap,
+                                 reinterpret_cast<unsigned long long *>(d_result), t->cfg.device, s);
+    });
+}
+
+int hkv_table_fetch_async(hkv_table *t, const uint64_t *d_keys, uint64_t n, void *d_records,
+                          hkv_fetch_result *d_result, void *stream)
+{
+    if (int rc = key_pass_enter(t, d_keys, n, d_records, n, d_result, "fetch")) return rc;
+    PASS_DETAIL(d, " %llu keys", (unsigned long long)n);
+    return table_pass(t, stream, "fetch", d, [&](const uint8_t *line, hipStream_t s) {
+        return launch_table_fetch(t->geo, t->d_index, t->d_log, line,
+                                  reinterpret_cast<const unsigned long long *>(d_keys), n,
+                                  static_cast<uint8_t *>(d_records), reinterpret_cast<unsigned long long *>(d_result),
+                                  t->cfg.device, s);
+    });
+}
+
 // Upsert (hermeskv.h "Upsert"): the install with a missed flag per record through table_pass (the table as it is,
 // nothing converted), the one host read that decides the rest (the install's counts), and, when anything was
 // missed, the table to LOG as before a populate and the inserts into index and log (launch_upsert_inserts). The

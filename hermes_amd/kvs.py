@@ -171,6 +171,70 @@ class Extract:
         return self.tensor[:n * self.entry].cpu().numpy().reshape(n, self.entry)
 
 
+SUMMARY_BYTES = 16   # hkv_key_summary
+SUMMARY_DTYPE = np.dtype([("key", "<u8"), ("ts_ver", "<u4"), ("ts_cid", "u1"), ("state", "u1"), ("zero", "u1", (2,))])
+NEED_FIELDS = ("missed", "newer", "validate", "same", "state_only", "older", "needed")   # hkv_need_result's words
+FETCH_FIELDS = ("found", "absent")
+
+
+@dataclasses.dataclass
+class Summaries(Extract):
+    """The result of HermesKV.summaries(), still on the device: an Extract whose buffer holds 16-byte key summaries
+    (include/hermeskv.h "Key-level delta repair": key, ts version, ts cid, state) instead of records; `entry` is
+    16. records, scanned_keys and written mean what they mean there and synchronise."""
+
+    def summaries_host(self) -> np.ndarray:
+        """the written summaries as a SUMMARY_DTYPE array, in no particular order"""
+        return self.records_host().reshape(-1).view(SUMMARY_DTYPE)
+
+
+@dataclasses.dataclass
+class Need:
+    """The result of HermesKV.need(), still on the device. `keys`: int64[cap], of which the first min(needed, cap)
+    are the needed keys in no particular order; `result`: hkv_need_result's first seven words as int64 (missed,
+    newer, validate, same, state_only, older, needed). host() and the attributes of those names synchronise."""
+    keys: torch.Tensor
+    result: torch.Tensor
+
+    def host(self) -> dict:
+        return {k: int(x) & 0xFFFFFFFFFFFFFFFF for k, x in zip(NEED_FIELDS, self.result.cpu().tolist())}
+
+    def __getattr__(self, name: str):
+        if name in NEED_FIELDS:
+            return self.host()[name]
+        raise AttributeError(name)
+
+    @property
+    def written(self) -> int:
+        return min(self.host()["needed"], self.keys.numel())
+
+    def keys_host(self) -> np.ndarray:
+        """the listed keys (uint64), min(needed, capacity) of them, in no particular order"""
+        return self.keys[:self.written].cpu().numpy().view(np.uint64)
+
+
+@dataclasses.dataclass
+class Fetch:
+    """The result of HermesKV.fetch(), still on the device. `tensor`: uint8[n x E], record i the record of key i
+    (zero but for its key bytes where the table does not hold the key); `result`: found, absent as int64.
+    host() and the two attributes synchronise."""
+    tensor: torch.Tensor
+    result: torch.Tensor
+    entry: int
+
+    def host(self) -> dict:
+        return {k: int(x) & 0xFFFFFFFFFFFFFFFF for k, x in zip(FETCH_FIELDS, self.result.cpu().tolist())}
+
+    def __getattr__(self, name: str):
+        if name in FETCH_FIELDS:
+            return self.host()[name]
+        raise AttributeError(name)
+
+    def records_host(self) -> np.ndarray:
+        """the records as [n][E] uint8, in key order"""
+        return self.tensor.cpu().numpy().reshape(-1, self.entry)
+
+
 PART_FIELDS = ("digest_sum", "digest_xor", "keys", "not_valid")   # hkv_part_row's words
 
 
@@ -639,6 +703,93 @@ class HermesKV:
               "hkv_table_upsert")
         self.num_keys += int(out.inserted)
         return {name: int(getattr(out, name)) for name, _ in HkvUpsertResult._fields_[:7]}
+
+    # -- key-level delta repair (include/hermeskv.h, "Key-level delta repair")
+    def summaries(self, bkt_range: tuple[int, int] | None = None, min_ts: int = 0, part_bits: int | None = None,
+                  part_mask: torch.Tensor | None = None, out: torch.Tensor | None = None, cap: int | None = None,
+                  stream: torch.cuda.Stream | None = None) -> "Summaries":
+        """hkv_table_summaries_async: one 16-byte summary (key, ts version, ts cid, state) per live key that
+        extract() with the same bkt_range, min_ts, part_bits and part_mask would emit a record for, compacted in no
+        particular order, read from whichever residency the table is in (nothing is converted), asynchronously on
+        `stream` (default: torch's current). part_mask None: every partition (part_bits then defaults to 0).
+        out: a uint8 device buffer to write into (its whole summaries are the capacity) instead of a new one of
+        `cap` summaries (default: the table's num_keys). Summaries past the capacity are counted, not written.
+        Read-only; not for tables with RMWs."""
+        dev = torch.device("cuda", self.device)
+        part_bits = 0 if part_bits is None else int(part_bits)
+        if out is None:
+            n_cap = int(self.num_keys if cap is None else cap)
+            out = torch.empty(max(n_cap, 1) * SUMMARY_BYTES, dtype=torch.uint8, device=dev)
+        else:
+            assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()
+            n_cap = out.numel() // SUMMARY_BYTES if cap is None else int(cap)
+            assert n_cap * SUMMARY_BYTES <= out.numel()
+        result = torch.empty(2, dtype=torch.int64, device=dev)
+        lo, hi = (0, self.cfg.num_bkts) if bkt_range is None else (int(bkt_range[0]), int(bkt_range[1]))
+        if part_mask is not None:
+            assert part_mask.is_cuda and part_mask.dtype == torch.uint8 and part_mask.is_contiguous()
+            assert part_bits >= 64 or part_mask.numel() >= 1 << part_bits
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_summaries_async(self.h, part_bits & 0xFFFFFFFF,
+                                           ctypes.c_void_p(part_mask.data_ptr()) if part_mask is not None else None,
+                                           lo, hi, int(min_ts), ctypes.c_void_p(out.data_ptr()), n_cap,
+                                           ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)),
+              "hkv_table_summaries_async")
+        return Summaries(out[:n_cap * SUMMARY_BYTES], result, SUMMARY_BYTES)
+
+    def need(self, summaries, n: int | None = None, out: torch.Tensor | None = None,
+             stream: torch.cuda.Stream | None = None) -> "Need":
+        """hkv_table_need_async: look the n summaries up (a Summaries, or a contiguous uint8 / int64 device tensor
+        of whole summaries) and class each against this table's entry: missed, newer, validate (equal timestamp,
+        the summary VALID, the entry not), same, state_only, older. A key is needed exactly when installing its
+        record would miss or change a byte the digest keeps: missed, newer and validate. Returns a Need: the needed
+        keys compacted (int64, no particular order; `out`: a tensor to write them into, whose length is the
+        capacity, instead of a new one of n) and the seven counts, all still on the device. n omitted: for a
+        Summaries min(records, capacity), read on the host (pass n to stay on the stream); for a tensor, all of
+        it. Nothing is written to the table; duplicates among the summaries are harmless. Not for tables with RMWs."""
+        t = summaries.tensor if isinstance(summaries, Summaries) else summaries
+        assert t.is_cuda and t.dtype in (torch.uint8, torch.int64) and t.is_contiguous()
+        if n is None:
+            n = summaries.written if isinstance(summaries, Summaries) else t.numel() * t.element_size() // SUMMARY_BYTES
+        n = int(n)
+        assert 0 <= n and n * SUMMARY_BYTES <= t.numel() * t.element_size()
+        if out is None:
+            out = torch.empty(max(n, 2), dtype=torch.int64, device=t.device)
+            need_cap = n
+        else:
+            assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous()
+            need_cap = out.numel()
+        result = torch.empty(8, dtype=torch.int64, device=t.device)
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_need_async(self.h, ctypes.c_void_p(t.data_ptr()) if n else None, n,
+                                      ctypes.c_void_p(out.data_ptr()) if need_cap else None, need_cap,
+                                      ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)), "hkv_table_need_async")
+        return Need(out[:need_cap], result[:7])
+
+    def fetch(self, keys, n: int | None = None, out: torch.Tensor | None = None,
+              stream: torch.cuda.Stream | None = None) -> "Fetch":
+        """hkv_table_fetch_async: the records of n keys (a Need, or a contiguous int64 device tensor), by position:
+        record i is key i's, in extract()'s record format, read from whichever residency the table is in (nothing
+        is converted). A key the table does not hold gives a record that is zero but for its key bytes and counts
+        as absent; a key may repeat. out: a uint8 device buffer of n * E bytes or more to write into instead of a
+        new one. n omitted: for a Need min(needed, capacity), read on the host; for a tensor, all of it. Read-only;
+        not for tables with RMWs."""
+        E = self.sizes.entry
+        t = keys.keys if isinstance(keys, Need) else keys
+        assert t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()
+        if n is None:
+            n = keys.written if isinstance(keys, Need) else t.numel()
+        n = int(n)
+        assert 0 <= n <= t.numel()
+        if out is None:
+            out = torch.empty(max(n, 1) * E, dtype=torch.uint8, device=t.device)
+        assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n * E
+        result = torch.empty(2, dtype=torch.int64, device=t.device)
+        s = (stream or torch.cuda.current_stream(self.device)).cuda_stream
+        check(_L.hkv_table_fetch_async(self.h, ctypes.c_void_p(t.data_ptr()) if n else None, n,
+                                       ctypes.c_void_p(out.data_ptr()) if n else None,
+                                       ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)), "hkv_table_fetch_async")
+        return Fetch(out[:n * E], result, E)
 
     def device_index(self) -> int:
         return _L.hkv_device_index(self.h)

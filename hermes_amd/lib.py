@@ -130,6 +130,13 @@ _L.hkv_table_extract_parts_async.argtypes = [_P, ctypes.c_uint32, _P, ctypes.c_u
 _L.hkv_upsert_result_bytes.restype = ctypes.c_uint32
 _L.hkv_table_upsert.argtypes = [_P, _P, ctypes.c_uint64, ctypes.POINTER(HkvUpsertResult), _P]
 _L.hkv_debug_upsert_phases.argtypes = [_P, ctypes.POINTER(ctypes.c_float)]
+_L.hkv_key_summary_bytes.restype = ctypes.c_uint32
+_L.hkv_need_result_bytes.restype = ctypes.c_uint32
+_L.hkv_fetch_result_bytes.restype = ctypes.c_uint32
+_L.hkv_table_summaries_async.argtypes = [_P, ctypes.c_uint32, _P, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _P,
+                                         ctypes.c_uint64, _P, _P]
+_L.hkv_table_need_async.argtypes = [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]
+_L.hkv_table_fetch_async.argtypes = [_P, _P, ctypes.c_uint64, _P, _P, _P]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

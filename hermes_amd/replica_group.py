@@ -999,6 +999,180 @@ def group_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part
     return out
 
 
+NEED_CLASSES = ("missed", "newer", "validate", "same", "state_only", "older")   # hkv_need_result's first six words
+
+
+def _key_delta_bytes(E: int, summaries: int, needed: int) -> dict:
+    """what a key-level repair ships, beside what the partitioned delta would have shipped for the same partitions"""
+    return {"bytes_summaries": 16 * summaries, "bytes_keys": 8 * needed, "bytes_records": E * needed,
+            "bytes_partition_delta": E * summaries}
+
+
+def key_delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chunk_buckets: int | None = None,
+                     insert: bool = False) -> dict:
+    """delta_resync() that ships key summaries first and then only the records `dst` needs (include/hermeskv.h,
+    "Key-level delta repair"), both tables in this process. In this order: both partition censuses and part_diff,
+    as delta_resync(); one host read of the source's key count in the differing partitions -- the exact summary
+    count; HermesKV.summaries of `src` for those partitions (16 bytes per key); HermesKV.need of `dst` (the keys
+    whose install would miss or change a digest byte: missed, newer, validate); one host read of `needed`;
+    HermesKV.fetch of those keys from `src` (every one must be found there); install into `dst` (insert=True:
+    upsert); the partition census of `dst` again. With chunk_buckets the source is walked in chunks of that many
+    buckets, each through all of these steps, with a host read of each chunk's summary count as well.
+    Returns delta_resync()'s fields -- the install counts {raised, equal, older, missed} (and inserted, replaced,
+    evictions with insert), records (the records fetched and installed: needed), scanned_keys, partitions,
+    differing_before, differing_after, unresolved -- plus summaries, needed, classes (the six class counts of the
+    need pass by name) and the bytes shipped: bytes_summaries = 16 summaries, bytes_keys = 8 needed, bytes_records =
+    E needed, beside bytes_partition_delta = E summaries, what delta_resync() ships for the same partitions.
+    The need list holds the keys `dst` lacks without saying which they are, so they are fetched too; without
+    insert their records are `missed` by the install, as in delta_resync(). Every limit of a repair holds: `dst` is
+    quiet meanwhile, no tables with RMWs, nobody is re-admitted to the membership, and a partition that still
+    differs is reported in unresolved, never hidden (`dst` newer in a key: class `older`; a key it lacks, without
+    insert: `missed`; keys lost to `replaced` / `evictions` with it)."""
+    assert dst.sizes == src.sizes, "records of one entry size only"
+    if part_bits is None:
+        part_bits = min(20, _log2_buckets(min(src.cfg.num_bkts, dst.cfg.num_bkts)))
+    part_bits = int(part_bits)
+    dev = torch.device("cuda", src.device)
+    E = src.sizes.entry
+    rows = src.census_parts(part_bits).tensor
+    mask, count = part_diff(rows, dst.census_parts(part_bits))
+    n, differing = _selected_keys(rows, mask, count)
+    sink = _RecordSink(dst, insert, dev)
+    classes = torch.zeros(6, dtype=torch.int64, device=dev)
+    absent = torch.zeros(1, dtype=torch.int64, device=dev)
+    summaries = scanned = needed = 0
+    if n:
+        chunks = _bucket_chunks(src.cfg.num_bkts, chunk_buckets)
+        sbuf = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        kbuf = torch.empty(max(n, 2), dtype=torch.int64, device=dev)
+        for lo, hi in chunks:
+            sm = src.summaries((lo, hi), part_bits=part_bits, part_mask=mask, out=sbuf)
+            # (the whole table at once: its summary count is n, checked with the read of `needed` below)
+            m = n if len(chunks) == 1 else sm.records
+            nd = dst.need(sm, n=m, out=kbuf[:max(m, 1)])
+            h = [int(v) for v in torch.cat([sm.result, nd.result]).cpu().tolist()]
+            assert h[0] == m, "the selected partitions' key counts are the summaries' count"
+            summaries, scanned, k = summaries + h[0], scanned + h[1], h[2 + 6]
+            classes += nd.result[:6]
+            needed += k
+            if k:
+                f = src.fetch(nd, n=k)
+                absent += f.result[1:2]
+                sink(f.tensor, k)
+        assert summaries == n, "the selected partitions' key counts are the summaries' count"
+        assert int(absent.cpu()[0]) == 0, "the source does not hold a key it summarised"
+    out = sink.result()
+    out.update(records=needed, scanned_keys=scanned, partitions=1 << part_bits, differing_before=differing,
+               summaries=summaries, needed=needed, classes=dict(zip(NEED_CLASSES, (int(v) for v in classes.cpu().tolist()))))
+    out.update(_key_delta_bytes(E, summaries, needed))
+    out.update(_delta_verify(dst, rows, part_bits))
+    return out
+
+
+def group_key_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part_bits: int | None,
+                           chunk_buckets: int | None, insert: bool = False) -> dict:
+    """key_delta_resync() across ranks. Collective: every rank of `group` calls it with the same arguments and its
+    own table (tables of one entry size; bucket counts may differ). Rows, masks and the summary count as in
+    group_delta_resync(): the source broadcasts its partition rows, each stale rank diffs them against its own, the
+    masks are united (all_reduce MAX). Then, per chunk of chunk_buckets buckets of the source (default: the whole
+    table): the source broadcasts its summaries of the united partitions; each stale rank computes its need list;
+    the lists reach the source padded to the longest (an all_reduce MAX of the counts, read on the host, then one
+    all_gather of count + keys); the source fetches the unique union of them (torch.unique) once and broadcasts
+    its size and the records; every stale rank installs them (insert=True: upserts). A record only another rank
+    needed is `equal` or `older` here and does no harm, the install being timestamp-guarded.
+    Returns this rank's install counts (zeros where it did not install), records (the union's size), scanned_keys,
+    partitions, selected, summaries, this rank's needed and classes (zeros where it is not stale), the bytes the
+    source broadcast (bytes_summaries, bytes_records = E records), bytes_keys = 8 x this rank's needed, beside
+    bytes_partition_delta = E summaries, and this rank's differing_before, differing_after and unresolved. The
+    conditions are key_delta_resync()'s: a stale rank takes no client operations meanwhile, no tables with RMWs,
+    nobody is re-admitted to the membership here, and a partition that still differs is reported in unresolved."""
+    import torch.distributed as dist
+    rank = dist.get_rank(group)
+    world = dist.get_world_size(group)
+    src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
+    stale = {int(r) for r in stale_ranks}
+    assert source_rank not in stale
+    dev = torch.device("cuda", kvs.device)
+    E = kvs.sizes.entry
+    geo = torch.tensor([kvs.cfg.num_bkts, _log2_buckets(kvs.cfg.num_bkts)], dtype=torch.int64, device=dev)
+    low = geo[1:].clone()
+    dist.broadcast(geo, src, group=group)
+    dist.all_reduce(low, op=dist.ReduceOp.MIN, group=group)
+    num_bkts, most_bits = int(geo[0].cpu()), int(low.cpu()[0])
+    part_bits = min(20, most_bits) if part_bits is None else int(part_bits)
+    assert part_bits <= most_bits, "part_bits above log2 of a rank's bucket count"
+    P = 1 << part_bits
+    mine = kvs.census_parts(part_bits).tensor
+    rows = mine.clone()
+    dist.broadcast(rows, src, group=group)
+    mask = torch.zeros(P, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if rank in stale:
+        mask, count = part_diff(rows, mine)
+    differing = count.clone()
+    dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=group)
+    n, selected = _selected_keys(rows, mask, (mask != 0).sum().reshape(1))
+    sink = _RecordSink(kvs, insert, dev)
+    classes = torch.zeros(6, dtype=torch.int64, device=dev)
+    summaries = scanned = needed = records = 0
+    if n:
+        sbuf = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        res = torch.zeros(2, dtype=torch.int64, device=dev)
+        for lo, hi in _bucket_chunks(num_bkts, chunk_buckets):
+            if rank == source_rank:
+                res = kvs.summaries((lo, hi), part_bits=part_bits, part_mask=mask, out=sbuf).result
+            dist.broadcast(res, src, group=group)
+            m, sc = (int(v) for v in res.cpu().tolist())
+            assert summaries + m <= n, "more summaries than the selected partitions' keys"
+            summaries, scanned = summaries + m, scanned + sc
+            if not m:
+                continue
+            dist.broadcast(sbuf[:m * 16], src, group=group)
+            # this rank's need list, then the longest list's length (every rank reads it: it sizes the gather)
+            k = torch.zeros(1, dtype=torch.int64, device=dev)
+            nd = None
+            if rank in stale:
+                nd = kvs.need(sbuf, n=m)
+                classes += nd.result[:6]
+                k = nd.result[6:7].clone()
+            most = k.clone()
+            dist.all_reduce(most, op=dist.ReduceOp.MAX, group=group)
+            k_host, most_host = (int(v) for v in torch.cat([k, most]).cpu().tolist())
+            needed += k_host
+            if not most_host:
+                continue
+            send = torch.zeros(1 + most_host, dtype=torch.int64, device=dev)   # count, keys, padding
+            send[0:1] = k
+            if k_host:
+                send[1:1 + k_host] = nd.keys[:k_host]
+            lists = torch.empty(world * (1 + most_host), dtype=torch.int64, device=dev)
+            dist.all_gather_into_tensor(lists, send, group=group)
+            u = torch.zeros(1, dtype=torch.int64, device=dev)
+            rbuf = None
+            if rank == source_rank:
+                counts = [int(c) for c in lists.view(world, -1)[:, 0].cpu().tolist()]
+                union = torch.unique(torch.cat([lists.view(world, -1)[r, 1:1 + c] for r, c in enumerate(counts)]))
+                f = kvs.fetch(union.contiguous())
+                assert f.absent == 0, "the source does not hold a key it summarised"
+                rbuf, u[0] = f.tensor, union.numel()
+            dist.broadcast(u, src, group=group)
+            u_host = int(u.cpu()[0])
+            if rbuf is None:
+                rbuf = torch.empty(u_host * E, dtype=torch.uint8, device=dev)
+            dist.broadcast(rbuf, src, group=group)
+            records += u_host
+            if rank in stale:
+                sink(rbuf, u_host)
+    out = sink.result()
+    out.update(records=records, scanned_keys=scanned, partitions=P, selected=selected, summaries=summaries,
+               needed=needed, classes=dict(zip(NEED_CLASSES, (int(v) for v in classes.cpu().tolist()))),
+               differing_before=int(differing.cpu()[0]))
+    out.update(_key_delta_bytes(E, summaries, needed))
+    out["bytes_records"] = E * records
+    out.update(_delta_verify(kvs, rows, part_bits) if rank in stale else {"differing_after": 0, "unresolved": []})
+    return out
+
+
 class LoopbackGroup:
     """N replicas driven phase by phase in one process; the collectives are tensor copies with
     exactly the layouts the RCCL driver produces (all-gather: row p = rank p's slab;

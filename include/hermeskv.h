@@ -537,6 +537,86 @@ int hkv_table_upsert(hkv_table *t, const void *d_records, uint64_t n, hkv_upsert
  * without the variable. */
 int hkv_debug_upsert_phases(const hkv_table *t, float *ms5);
 
+/* Key-level delta repair (ABI 10, functions only): key summaries first, then only the records needed. The
+ * partition rows say where two replicas differ, never which key, so a delta repair ships every record of a differing
+ * partition. Three read-only calls close the gap: the source sends a 16-byte summary per key of those partitions,
+ * the target answers with the keys it needs, and the source sends the records of those keys alone.
+ *
+ * Summary (hkv_key_summary, 16 bytes): bytes 0..7 the key (entry bytes 8..15), 8..11 the ts version, 12 the ts cid,
+ * 13 the state byte, 14..15 zero. A summary is a function of its record (and so of the entry's digest bytes).
+ *
+ * hkv_table_summaries_async. One summary per live slot that hkv_table_extract_parts_async with the same part_bits,
+ * mask, bucket range and min_ts would emit a record for, compacted to d_summaries in no particular order. A NULL
+ * d_part_mask selects every partition (part_bits is still checked). records, scanned_keys, cap and "nothing at or
+ * past min(records, cap) * 16 bytes is touched" mean what they mean for the extract. Only the first 32 bytes of
+ * an entry are read, whatever the entry size.
+ *
+ * hkv_table_need_async. Each of the n summaries is looked up as the reference looks a key up (first in-use tag
+ * match, window check, 8-byte key compare) and classed against the table's entry, by packed timestamp
+ * (version << 8 | cid):
+ *   missed      the table does not hold the key
+ *   newer       summary ts > entry ts
+ *   validate    equal ts, summary state VALID, entry state not VALID
+ *   same        equal ts and equal state byte
+ *   state_only  equal ts, the state bytes differ, and an install would not change the entry's state (the summary's
+ *               state is not VALID)
+ *   older       summary ts < entry ts
+ * THE RULE: a key is *needed* exactly when installing its record would miss, or would change a byte of the entry
+ * that the digest keeps. That is missed, newer and validate: a newer record installs timestamp, value and state; a
+ * record of equal timestamp changes a digest byte only through its VAL, which sets the state to VALID where it was
+ * not; an older record changes nothing. (An equal record also rewrites the last-writer bits, which the digest leaves
+ * out.) The needed keys, 8 bytes each, are written compacted to d_need_keys in no particular order; `needed` may
+ * exceed need_cap, and nothing at or past min(needed, need_cap) * 8 bytes is touched. d_result is overwritten, not
+ * accumulated. Nothing is written to the table, so a key may occur any number of times among the summaries (each
+ * occurrence is classed and, if needed, listed).
+ *
+ * hkv_table_fetch_async. Positional: record i, at d_records + i * E, is the record (see "Replica repair": the entry
+ * image under the digest's mask) of key d_keys[i]. A key the table does not hold gives a record that is zero but for
+ * the key in bytes 8..15 (state 0 is no hermes state: such a record is recognisable). A key may occur any number of
+ * times. found + absent = n.
+ *
+ * All three follow the census's rules: the table is read as it is (an INLINE table's inline keys from their lines,
+ * never from their stale log copies); nothing is converted and conversions / inline_launches do not move; the call is
+ * asynchronous on `stream`, ordered after the table's last stream, takes one caller at a time, and stops a live
+ * serving kernel first. None writes the table. Refusals, with a negative code and a message in hkv_last_error() that
+ * names the call (summaries, need, fetch), before anything is launched: a NULL table or result; a NULL buffer whose
+ * count (cap, n, need_cap) is not zero; a buffer or result that is not 16-byte aligned; a table with rmw_enabled (the
+ * extract's reason: what these calls produce feeds the install); for the summaries also bkt_hi > num_bkts,
+ * bkt_lo > bkt_hi and part_bits > log2(num_bkts).
+ *
+ * A key-level repair (hermes_amd.replica_group.key_delta_resync) is: both partition censuses and the diff, as in
+ * a delta repair; the source's summaries of the differing partitions; the target's need list; the source's fetch
+ * of it; the install (or the upsert) into the target; the target's partition census again. It ships 16 bytes per
+ * key of the differing partitions, 8 per needed key and E per needed key, where the delta repair ships E per key
+ * of the differing partitions. Every limit of a repair holds. */
+typedef struct hkv_key_summary {
+    uint64_t key;                /* entry bytes 8..15 */
+    uint32_t ts_version;
+    uint8_t  ts_cid;
+    uint8_t  state;
+    uint8_t  zero[2];
+} hkv_key_summary;
+typedef struct hkv_need_result {
+    uint64_t missed, newer, validate;   /* the needed classes */
+    uint64_t same, state_only, older;   /* the others */
+    uint64_t needed;                    /* missed + newer + validate (may exceed need_cap) */
+    uint64_t reserved;                  /* zero */
+} hkv_need_result;
+typedef struct hkv_fetch_result {
+    uint64_t found;              /* keys the table holds */
+    uint64_t absent;             /* keys it does not: zero records but for the key */
+} hkv_fetch_result;
+uint32_t hkv_key_summary_bytes(void);    /* sizeof(hkv_key_summary) = 16, for bindings */
+uint32_t hkv_need_result_bytes(void);    /* sizeof(hkv_need_result) = 64 */
+uint32_t hkv_fetch_result_bytes(void);   /* sizeof(hkv_fetch_result) = 16 */
+int hkv_table_summaries_async(hkv_table *t, uint32_t part_bits, const uint8_t *d_part_mask, uint64_t bkt_lo,
+                              uint64_t bkt_hi, uint64_t min_ts, void *d_summaries, uint64_t cap,
+                              hkv_extract_result *d_result, void *stream);
+int hkv_table_need_async(hkv_table *t, const void *d_summaries, uint64_t n, uint64_t *d_need_keys, uint64_t need_cap,
+                         hkv_need_result *d_result, void *stream);
+int hkv_table_fetch_async(hkv_table *t, const uint64_t *d_keys, uint64_t n, void *d_records,
+                          hkv_fetch_result *d_result, void *stream);
+
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
 hkv_table *hkv_default_table(void);
