@@ -231,6 +231,15 @@ int launch_table_need(const Geometry &g, const uint8_t *index, const uint8_t *lo
 int launch_table_fetch(const Geometry &g, const uint8_t *index, const uint8_t *log, const uint8_t *line,
                        const unsigned long long *keys, uint64_t n, uint8_t *records, unsigned long long *result,
                        int device, hipStream_t s);
+// Sketch-level delta repair (hermeskv.h "Sketch-level delta repair", hkv_sketch.hip). Fold: n summaries into the
+// 3 S cells, zeroed first unless accumulate. Decode: a -= b, the passes and the closing count, all enqueued at once;
+// result[0..7] (hkv_sketch_result) zeroed first. api_fail: hkv_last_error()'s message for entry points outside
+// hkv_runtime.hip; returns code.
+int launch_sketch_fold(const uint8_t *summaries, uint64_t n, void *cells, uint64_t S, int accumulate, int device,
+                       hipStream_t s);
+int launch_sketch_decode(void *a, const void *b, uint64_t S, uint8_t *only_a, uint64_t cap_a, uint8_t *only_b,
+                         uint64_t cap_b, unsigned long long *result, int device, hipStream_t s);
+int api_fail(int code, const char *msg);
 // The upsert's inserts (hermeskv.h "Upsert", step 2) into index and log, after an install with missed_flag and the
 // host's read of its missed count m (1 <= m <= n <= 2^31 - 1): the scan of the flags into ranks, the missed
 // records' (bucket, rank) pairs, their stable sort by bucket, the per-bucket replay of mica_insert_one, and the

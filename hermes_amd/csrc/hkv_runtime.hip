@@ -232,6 +232,7 @@ static int fail(int code, const char *fmt, ...)
     g_err = buf;
     return code;
 }
+int hkv::api_fail(int code, const char *msg) { return fail(code, "%s", msg); }
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \

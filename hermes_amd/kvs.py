@@ -806,3 +806,118 @@ def hash_ids(ids: torch.Tensor, stream: torch.cuda.Stream | None = None) -> torc
     check(_L.hkv_hash_ids(ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(out.data_ptr()), ids.numel(),
                           ctypes.c_void_p(s)), "hkv_hash_ids")
     return out
+
+
+# ---------------------------------------------------------------- sketch-level delta repair
+SKETCH_CELL_BYTES = 32   # hkv_sketch_cell: count, key_xor, meta_xor, check_xor
+SKETCH_MAX_PASSES = 192  # HKV_SKETCH_MAX_PASSES
+SKETCH_FIELDS = ("only_a", "only_b", "undecoded", "passes", "exhausted")   # hkv_sketch_result's first five words
+
+
+def _u64(x) -> int:
+    return int(x) & 0xFFFFFFFFFFFFFFFF
+
+
+@dataclasses.dataclass
+class Sketch:
+    """The result of sketch(), still on the device. `cells`: int64[3 * sub_cells, 4], cell i = hkv_sketch_cell
+    (count, key_xor, meta_xor, check_xor: the unsigned words' bit patterns) of include/hermeskv.h "Sketch-level
+    delta repair"; subtable j is rows [j * sub_cells, (j + 1) * sub_cells). host() synchronises."""
+    cells: torch.Tensor
+    sub_cells: int
+
+    @property
+    def nbytes(self) -> int:
+        return 3 * self.sub_cells * SKETCH_CELL_BYTES
+
+    def host(self) -> np.ndarray:
+        """the cells as uint64 [3 * sub_cells, 4]"""
+        return self.cells.cpu().numpy().view(np.uint64)
+
+
+@dataclasses.dataclass
+class SketchDecode:
+    """The result of sketch_decode(), still on the device. `only_a`, `only_b`: uint8 buffers of cap_a, cap_b
+    16-byte summaries, of which the first min(count, cap) are the elements taken, in no particular order;
+    `result`: hkv_sketch_result as eight int64 words; `remainder`: the Sketch that went in as `a`, now holding the
+    2-core. host(), the attributes named in SKETCH_FIELDS, only_a_host() and only_b_host() synchronise."""
+    only_a: torch.Tensor
+    only_b: torch.Tensor
+    result: torch.Tensor
+    remainder: Sketch
+
+    def host(self) -> dict:
+        return {k: _u64(x) for k, x in zip(SKETCH_FIELDS, self.result.cpu().tolist())}
+
+    def __getattr__(self, name: str):
+        if name in SKETCH_FIELDS:
+            return self.host()[name]
+        raise AttributeError(name)
+
+    def _list_host(self, buf: torch.Tensor, count: int) -> np.ndarray:
+        n = min(count, buf.numel() // SUMMARY_BYTES)
+        return buf[:n * SUMMARY_BYTES].cpu().numpy().view(SUMMARY_DTYPE)
+
+    def only_a_host(self) -> np.ndarray:
+        """the summaries only `a` held, min(only_a, cap_a) of them as a SUMMARY_DTYPE array"""
+        return self._list_host(self.only_a, self.host()["only_a"])
+
+    def only_b_host(self) -> np.ndarray:
+        """the summaries only `b` held, min(only_b, cap_b) of them as a SUMMARY_DTYPE array"""
+        return self._list_host(self.only_b, self.host()["only_b"])
+
+
+def sketch(summaries, sub_cells: int, n: int | None = None, out: "Sketch | torch.Tensor | None" = None,
+           accumulate: bool = False, stream: torch.cuda.Stream | None = None) -> Sketch:
+    """hkv_summaries_sketch_async: fold n 16-byte summaries (a Summaries, or a contiguous uint8 / int64 device
+    tensor of whole summaries) into an invertible sketch of 3 * sub_cells cells (include/hermeskv.h "Sketch-level
+    delta repair"), asynchronously on `stream` (default: torch's current). The cells are a function of the multiset
+    of summaries, so equal lists give equal bytes in whatever order. out: a Sketch of the same sub_cells, or an
+    int64 device tensor of 3 * sub_cells * 4 words, to fold into instead of a new one; accumulate: add to what `out`
+    holds instead of overwriting it. n omitted: for a Summaries min(records, capacity), read on the host (pass n to
+    stay on the stream); for a tensor, all of it."""
+    t = summaries.tensor if isinstance(summaries, Summaries) else summaries
+    assert t.is_cuda and t.dtype in (torch.uint8, torch.int64) and t.is_contiguous()
+    if n is None:
+        n = summaries.written if isinstance(summaries, Summaries) else t.numel() * t.element_size() // SUMMARY_BYTES
+    n, S = int(n), int(sub_cells)
+    assert 0 <= n and n * SUMMARY_BYTES <= t.numel() * t.element_size()
+    if out is None:
+        assert not accumulate, "accumulate adds to the cells of `out`"
+        cells = torch.empty((3 * S, 4), dtype=torch.int64, device=t.device)
+    else:
+        cells = out.cells if isinstance(out, Sketch) else out
+        assert cells.is_cuda and cells.dtype == torch.int64 and cells.is_contiguous() and cells.numel() == 12 * S
+        cells = cells.view(3 * S, 4)
+    with torch.cuda.device(t.device):
+        s = (stream or torch.cuda.current_stream(t.device)).cuda_stream
+        check(_L.hkv_summaries_sketch_async(ctypes.c_void_p(t.data_ptr()) if n else None, n,
+                                            ctypes.c_void_p(cells.data_ptr()), S, int(bool(accumulate)),
+                                            ctypes.c_void_p(s)), "hkv_summaries_sketch_async")
+    return Sketch(cells, S)
+
+
+def sketch_decode(a: Sketch, b: Sketch, cap_a: int | None = None, cap_b: int | None = None,
+                  stream: torch.cuda.Stream | None = None) -> SketchDecode:
+    """hkv_sketch_decode_async: subtract sketch `b` from sketch `a` (same sub_cells) and peel the difference. `a`
+    is overwritten: it ends as the remainder (all zero when the decode is complete). Returns a SketchDecode, still
+    on the device: the summaries only `a` held and those only `b` held (buffers of cap_a / cap_b summaries, default
+    3 * sub_cells each, which no decode can exceed by more than duplicates; counts past a cap are counted, not
+    written) and the result words (only_a, only_b, undecoded, passes, exhausted). Every kernel is enqueued up
+    front on `stream` (default: torch's current); nothing is read back until a count is asked for."""
+    assert a.sub_cells == b.sub_cells and a.cells.device == b.cells.device, "two sketches of one sub_cells"
+    assert a.cells.data_ptr() != b.cells.data_ptr()
+    S, dev = a.sub_cells, a.cells.device
+    cap_a = 3 * S if cap_a is None else int(cap_a)
+    cap_b = 3 * S if cap_b is None else int(cap_b)
+    la = torch.empty(max(cap_a, 1) * SUMMARY_BYTES, dtype=torch.uint8, device=dev)
+    lb = torch.empty(max(cap_b, 1) * SUMMARY_BYTES, dtype=torch.uint8, device=dev)
+    result = torch.empty(8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        s = (stream or torch.cuda.current_stream(dev)).cuda_stream
+        check(_L.hkv_sketch_decode_async(ctypes.c_void_p(a.cells.data_ptr()), ctypes.c_void_p(b.cells.data_ptr()), S,
+                                         ctypes.c_void_p(la.data_ptr()) if cap_a else None, cap_a,
+                                         ctypes.c_void_p(lb.data_ptr()) if cap_b else None, cap_b,
+                                         ctypes.c_void_p(result.data_ptr()), ctypes.c_void_p(s)),
+              "hkv_sketch_decode_async")
+    return SketchDecode(la[:cap_a * SUMMARY_BYTES], lb[:cap_b * SUMMARY_BYTES], result, a)

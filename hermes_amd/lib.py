@@ -137,6 +137,10 @@ _L.hkv_table_summaries_async.argtypes = [_P, ctypes.c_uint32, _P, ctypes.c_uint6
                                          ctypes.c_uint64, _P, _P]
 _L.hkv_table_need_async.argtypes = [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]
 _L.hkv_table_fetch_async.argtypes = [_P, _P, ctypes.c_uint64, _P, _P, _P]
+_L.hkv_sketch_cell_bytes.restype = ctypes.c_uint32
+_L.hkv_sketch_result_bytes.restype = ctypes.c_uint32
+_L.hkv_summaries_sketch_async.argtypes = [_P, ctypes.c_uint64, _P, ctypes.c_uint64, ctypes.c_int, _P]
+_L.hkv_sketch_decode_async.argtypes = [_P, _P, ctypes.c_uint64, _P, ctypes.c_uint64, _P, ctypes.c_uint64, _P, _P]
 _L.hkv_set_default_config.argtypes = [ctypes.POINTER(HkvConfig)]
 _L.hkv_default_table.restype = _P
 _L.hkv_hash_ids.argtypes = [_P, _P, ctypes.c_int64, _P]

@@ -1173,6 +1173,276 @@ def group_key_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, 
     return out
 
 
+def default_sub_cells(differing_partitions: int) -> int:
+    """a sketch-level repair's default S: 3 S >= 2.0 x (two elements per differing partition, the two versions of one
+    key), floor 32 -- 128 bytes of sketch per differing partition"""
+    return max(32, -(-4 * int(differing_partitions) // 3))
+
+
+def _fold_selected(kvs: HermesKV, part_bits: int, mask: torch.Tensor, n: int, S: int, chunk_buckets, dev):
+    """(the sketch of the table's summaries of the selected partitions, folded chunk by chunk into one sketch, and
+    [summaries, scanned keys] summed on the device). n: the table's key count in those partitions, which sizes the
+    summary buffer; with several chunks each chunk's count is read on the host."""
+    from .kvs import sketch
+    sk = None
+    tot = torch.zeros(2, dtype=torch.int64, device=dev)
+    sbuf = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=dev)
+    chunks = _bucket_chunks(kvs.cfg.num_bkts, chunk_buckets) if n else []
+    for lo, hi in chunks:
+        sm = kvs.summaries((lo, hi), part_bits=part_bits, part_mask=mask, out=sbuf)
+        tot += sm.result
+        sk = sketch(sm, S, n=n if len(chunks) == 1 else sm.records, out=sk, accumulate=sk is not None)
+    if sk is None:
+        sk = sketch(sbuf, S, n=0)
+    return sk, tot
+
+
+def _key_level_exchange(dst: HermesKV, src: HermesKV, part_bits: int, mask: torch.Tensor, n: int, chunk_buckets,
+                        sink: _RecordSink, dev) -> tuple:
+    """key_delta_resync()'s exchange for the selected partitions: per chunk the source's summaries, the target's
+    need list, the source's fetch, the records into `sink`. Returns (summaries, scanned, needed, classes tensor)."""
+    classes = torch.zeros(6, dtype=torch.int64, device=dev)
+    absent = torch.zeros(1, dtype=torch.int64, device=dev)
+    summaries = scanned = needed = 0
+    if n:
+        chunks = _bucket_chunks(src.cfg.num_bkts, chunk_buckets)
+        sbuf = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+        kbuf = torch.empty(max(n, 2), dtype=torch.int64, device=dev)
+        for lo, hi in chunks:
+            sm = src.summaries((lo, hi), part_bits=part_bits, part_mask=mask, out=sbuf)
+            m = n if len(chunks) == 1 else sm.records
+            nd = dst.need(sm, n=m, out=kbuf[:max(m, 1)])
+            h = [int(v) for v in torch.cat([sm.result, nd.result]).cpu().tolist()]
+            assert h[0] == m, "the selected partitions' key counts are the summaries' count"
+            summaries, scanned, k = summaries + h[0], scanned + h[1], h[2 + 6]
+            classes += nd.result[:6]
+            needed += k
+            if k:
+                f = src.fetch(nd, n=k)
+                absent += f.result[1:2]
+                sink(f.tensor, k)
+        assert summaries == n, "the selected partitions' key counts are the summaries' count"
+        assert int(absent.cpu()[0]) == 0, "the source does not hold a key it summarised"
+    return summaries, scanned, needed, classes
+
+
+def sketch_delta_resync(dst: HermesKV, src: HermesKV, part_bits: int | None = None, chunk_buckets: int | None = None,
+                        insert: bool = False, sub_cells: int | None = None) -> dict:
+    """key_delta_resync() that ships an invertible sketch where it ships summaries (include/hermeskv.h,
+    "Sketch-level delta repair"), both tables in this process. In this order: both partition censuses and
+    part_diff, as delta_resync(); one host read of both tables' key counts in the differing partitions and of the
+    number of those partitions; HermesKV.summaries of `src` and of `dst` for those partitions, the same mask on
+    both, each folded into one sketch of S = sub_cells cells per subtable (default default_sub_cells(differing
+    partitions)) -- with chunk_buckets each table is walked in chunks of that many of its own buckets, all folded
+    into the one sketch; sketch_decode(source's sketch, target's sketch), "at dst"; one host read of its result;
+    HermesKV.need of `dst` on only_a, the summaries only the source holds; one host read of `needed`;
+    HermesKV.fetch from `src`; install into `dst` (insert=True: upsert); the partition census of `dst` again.
+    When the decode is not complete (undecoded != 0, or more elements than the lists hold) the partial lists are
+    dropped and key_delta_resync()'s exchange runs instead: the source's summaries go to need.
+    Returns key_delta_resync()'s fields -- there `summaries` is the source's key count in the differing partitions
+    and bytes_summaries = 16 summaries what the key-level repair ships for them (and what was shipped after a
+    fallback); classes counts the summaries that reached need: only_src of them, or all after a fallback -- plus
+    sub_cells, only_src, only_dst (the decode's counts; only_dst is returned for a two-way repair and not used),
+    undecoded, passes, fallback, and bytes_sketch = 96 sub_cells, the sketch that crosses. Every limit of a repair
+    holds unchanged: `dst` is quiet meanwhile, no tables with RMWs, nobody is re-admitted to the membership, and a
+    partition that still differs is reported in unresolved, never hidden."""
+    from .kvs import sketch_decode
+    assert dst.sizes == src.sizes, "records of one entry size only"
+    if part_bits is None:
+        part_bits = min(20, _log2_buckets(min(src.cfg.num_bkts, dst.cfg.num_bkts)))
+    part_bits = int(part_bits)
+    dev = torch.device("cuda", src.device)
+    E = src.sizes.entry
+    rows = src.census_parts(part_bits).tensor
+    rows_dst = dst.census_parts(part_bits).tensor
+    mask, count = part_diff(rows, rows_dst)
+    sel = mask != 0
+    n, n_dst, differing = (int(v) for v in torch.stack([(rows[:, 2] * sel).sum(), (rows_dst[:, 2] * sel).sum(),
+                                                        count[0]]).cpu().tolist())
+    S = default_sub_cells(differing) if sub_cells is None else int(sub_cells)
+    sink = _RecordSink(dst, insert, dev)
+    classes = torch.zeros(6, dtype=torch.int64, device=dev)
+    scanned = needed = 0
+    dec = dict.fromkeys(("only_a", "only_b", "undecoded", "passes"), 0)
+    fallback = False
+    if differing:
+        sk_src, tot_src = _fold_selected(src, part_bits, mask, n, S, chunk_buckets, dev)
+        sk_dst, tot_dst = _fold_selected(dst, part_bits, mask, n_dst, S, chunk_buckets, dev)
+        d = sketch_decode(sk_src, sk_dst)
+        h = [int(v) for v in torch.cat([d.result[:4], tot_src, tot_dst]).cpu().tolist()]
+        dec = dict(zip(dec, h[:4]))
+        assert h[4] == n and h[6] == n_dst, "the selected partitions' key counts are the summaries' counts"
+        scanned = h[5]
+        fallback = dec["undecoded"] != 0 or dec["only_a"] > 3 * S or dec["only_b"] > 3 * S
+        if fallback:
+            _, sc, needed, classes = _key_level_exchange(dst, src, part_bits, mask, n, chunk_buckets, sink, dev)
+            scanned += sc
+        elif dec["only_a"]:
+            nd = dst.need(d.only_a, n=dec["only_a"])
+            classes = nd.result[:6]
+            needed = nd.needed
+            if needed:
+                f = src.fetch(nd, n=needed)
+                sink(f.tensor, needed)
+                assert f.absent == 0, "the source does not hold a key it summarised"
+    out = sink.result()
+    out.update(records=needed, scanned_keys=scanned, partitions=1 << part_bits, differing_before=differing,
+               summaries=n, needed=needed, classes=dict(zip(NEED_CLASSES, (int(v) for v in classes.cpu().tolist()))))
+    out.update(_key_delta_bytes(E, n, needed))
+    out.update(sub_cells=S, only_src=dec["only_a"], only_dst=dec["only_b"], undecoded=dec["undecoded"],
+               passes=dec["passes"], fallback=fallback, bytes_sketch=96 * S)
+    out.update(_delta_verify(dst, rows, part_bits))
+    return out
+
+
+def _group_need_exchange(kvs: HermesKV, group, src: int, is_source: bool, is_stale: bool, nd, sink: _RecordSink,
+                         dev) -> tuple:
+    """group_key_delta_resync()'s second half for one need list per stale rank (nd None elsewhere): the lists
+    reach the source padded to the longest, the source fetches their unique union once and broadcasts the records,
+    the stale ranks take them into `sink`. Returns (this rank's needed, the union's size)."""
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    E = kvs.sizes.entry
+    k = nd.result[6:7].clone() if nd is not None else torch.zeros(1, dtype=torch.int64, device=dev)
+    most = k.clone()
+    dist.all_reduce(most, op=dist.ReduceOp.MAX, group=group)
+    k_host, most_host = (int(v) for v in torch.cat([k, most]).cpu().tolist())
+    if not most_host:
+        return k_host, 0
+    send = torch.zeros(1 + most_host, dtype=torch.int64, device=dev)   # count, keys, padding
+    send[0:1] = k
+    if k_host:
+        send[1:1 + k_host] = nd.keys[:k_host]
+    lists = torch.empty(world * (1 + most_host), dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(lists, send, group=group)
+    u = torch.zeros(1, dtype=torch.int64, device=dev)
+    rbuf = None
+    if is_source:
+        counts = [int(c) for c in lists.view(world, -1)[:, 0].cpu().tolist()]
+        union = torch.unique(torch.cat([lists.view(world, -1)[r, 1:1 + c] for r, c in enumerate(counts)]))
+        f = kvs.fetch(union.contiguous())
+        assert f.absent == 0, "the source does not hold a key it summarised"
+        rbuf, u[0] = f.tensor, union.numel()
+    dist.broadcast(u, src, group=group)
+    u_host = int(u.cpu()[0])
+    if rbuf is None:
+        rbuf = torch.empty(u_host * E, dtype=torch.uint8, device=dev)
+    dist.broadcast(rbuf, src, group=group)
+    if is_stale:
+        sink(rbuf, u_host)
+    return k_host, u_host
+
+
+def group_sketch_delta_resync(kvs: HermesKV, group, source_rank: int, stale_ranks, part_bits: int | None,
+                              chunk_buckets: int | None, insert: bool = False, sub_cells: int | None = None) -> dict:
+    """sketch_delta_resync() across ranks, on group_key_delta_resync()'s choreography. Collective: every rank of
+    `group` calls it with the same arguments and its own table. Rows, masks and the source's key count as there: the
+    source broadcasts its partition rows, each stale rank diffs them against its own, the masks are united. Then
+    the source and every stale rank fold their own summaries of the united partitions into a sketch of S =
+    sub_cells cells per subtable (default default_sub_cells(partitions in the union)); the source broadcasts its
+    sketch, 96 S bytes; each stale rank decodes it against its own; an all_reduce MAX of `undecoded` (with a list
+    overflow counted as undecoded) decides the fallback for the whole call, so every rank takes the same branch.
+    Without it each stale rank's need list comes from its only_a; the lists reach the source, which fetches their
+    unique union once and broadcasts the records, as in group_key_delta_resync(). With it that function's exchange
+    runs per chunk: the source's summaries are broadcast and go to need.
+    Returns group_key_delta_resync()'s fields (summaries: the source's key count in the united partitions;
+    bytes_summaries what a key-level repair broadcasts for them, and what was broadcast after a fallback) plus
+    sub_cells, this rank's only_src, only_dst, undecoded and passes (zeros where it is not stale), fallback, and
+    bytes_sketch = 96 sub_cells. The conditions are sketch_delta_resync()'s."""
+    import torch.distributed as dist
+    from .kvs import Sketch, sketch_decode
+    rank = dist.get_rank(group)
+    src = dist.get_global_rank(group, source_rank) if group is not None else int(source_rank)
+    stale = {int(r) for r in stale_ranks}
+    assert source_rank not in stale
+    is_source, is_stale = rank == source_rank, rank in stale
+    dev = torch.device("cuda", kvs.device)
+    E = kvs.sizes.entry
+    geo = torch.tensor([kvs.cfg.num_bkts, _log2_buckets(kvs.cfg.num_bkts)], dtype=torch.int64, device=dev)
+    low = geo[1:].clone()
+    dist.broadcast(geo, src, group=group)
+    dist.all_reduce(low, op=dist.ReduceOp.MIN, group=group)
+    num_bkts, most_bits = int(geo[0].cpu()), int(low.cpu()[0])
+    part_bits = min(20, most_bits) if part_bits is None else int(part_bits)
+    assert part_bits <= most_bits, "part_bits above log2 of a rank's bucket count"
+    P = 1 << part_bits
+    mine = kvs.census_parts(part_bits).tensor
+    rows = mine.clone()
+    dist.broadcast(rows, src, group=group)
+    mask = torch.zeros(P, dtype=torch.uint8, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if is_stale:
+        mask, count = part_diff(rows, mine)
+    differing = count.clone()
+    dist.all_reduce(mask, op=dist.ReduceOp.MAX, group=group)
+    sel = mask != 0
+    n, n_own, selected = (int(v) for v in torch.stack([(rows[:, 2] * sel).sum(), (mine[:, 2] * sel).sum(),
+                                                       sel.sum()]).cpu().tolist())
+    S = default_sub_cells(selected) if sub_cells is None else int(sub_cells)
+    sink = _RecordSink(kvs, insert, dev)
+    classes = torch.zeros(6, dtype=torch.int64, device=dev)
+    summaries = scanned = needed = records = 0
+    dec = dict.fromkeys(("only_a", "only_b", "undecoded", "passes"), 0)
+    fallback = False
+    if selected:
+        own = tot = None
+        if is_source or is_stale:
+            own, tot = _fold_selected(kvs, part_bits, mask, n_own, S, chunk_buckets, dev)
+        cells = own.cells.clone() if is_source else torch.empty((3 * S, 4), dtype=torch.int64, device=dev)
+        stats = tot.clone() if is_source else torch.zeros(2, dtype=torch.int64, device=dev)
+        dist.broadcast(cells, src, group=group)
+        dist.broadcast(stats, src, group=group)
+        res = torch.zeros(4, dtype=torch.int64, device=dev)
+        d = None
+        if is_stale:
+            d = sketch_decode(Sketch(cells, S), own)
+            res = d.result[:4].clone()
+        over = ((res[0:1] > 3 * S) | (res[1:2] > 3 * S)).to(torch.int64)
+        und = torch.maximum(res[2:3], over)
+        dist.all_reduce(und, op=dist.ReduceOp.MAX, group=group)
+        h = [int(v) for v in torch.cat([res, und, stats]).cpu().tolist()]
+        dec = dict(zip(dec, h[:4]))
+        fallback = h[4] != 0
+        assert h[5] == n, "the selected partitions' key counts are the summaries' count"
+        summaries, scanned = n, h[6]
+        if not fallback:
+            nd = None
+            if is_stale:
+                nd = kvs.need(d.only_a, n=dec["only_a"])
+                classes += nd.result[:6]
+            needed, records = _group_need_exchange(kvs, group, src, is_source, is_stale, nd, sink, dev)
+        elif n:
+            summaries = 0
+            sbuf = torch.empty(n * 16, dtype=torch.uint8, device=dev)
+            sres = torch.zeros(2, dtype=torch.int64, device=dev)
+            for lo, hi in _bucket_chunks(num_bkts, chunk_buckets):
+                if is_source:
+                    sres = kvs.summaries((lo, hi), part_bits=part_bits, part_mask=mask, out=sbuf).result
+                dist.broadcast(sres, src, group=group)
+                m, sc = (int(v) for v in sres.cpu().tolist())
+                assert summaries + m <= n, "more summaries than the selected partitions' keys"
+                summaries, scanned = summaries + m, scanned + sc
+                if not m:
+                    continue
+                dist.broadcast(sbuf[:m * 16], src, group=group)
+                nd = None
+                if is_stale:
+                    nd = kvs.need(sbuf, n=m)
+                    classes += nd.result[:6]
+                k, u = _group_need_exchange(kvs, group, src, is_source, is_stale, nd, sink, dev)
+                needed, records = needed + k, records + u
+    out = sink.result()
+    out.update(records=records, scanned_keys=scanned, partitions=P, selected=selected, summaries=summaries,
+               needed=needed, classes=dict(zip(NEED_CLASSES, (int(v) for v in classes.cpu().tolist()))),
+               differing_before=int(differing.cpu()[0]))
+    out.update(_key_delta_bytes(E, summaries, needed))
+    out["bytes_records"] = E * records
+    out.update(sub_cells=S, only_src=dec["only_a"], only_dst=dec["only_b"], undecoded=dec["undecoded"],
+               passes=dec["passes"], fallback=fallback, bytes_sketch=96 * S)
+    out.update(_delta_verify(kvs, rows, part_bits) if is_stale else {"differing_after": 0, "unresolved": []})
+    return out
+
+
 class LoopbackGroup:
     """N replicas driven phase by phase in one process; the collectives are tensor copies with
     exactly the layouts the RCCL driver produces (all-gather: row p = rank p's slab;

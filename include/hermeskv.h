@@ -617,6 +617,81 @@ int hkv_table_need_async(hkv_table *t, const void *d_summaries, uint64_t n, uint
 int hkv_table_fetch_async(hkv_table *t, const uint64_t *d_keys, uint64_t n, void *d_records,
                           hkv_fetch_result *d_result, void *stream);
 
+/* Sketch-level delta repair (ABI 10, functions only): an invertible sketch where the key-level repair ships
+ * summaries. The partition rows cannot say which key of a differing partition differs, so a key-level repair ships
+ * the summary of every key of such a partition. With an invertible Bloom lookup table both sides fold their
+ * summaries of those partitions into a small table of cells, one table is shipped, the two are subtracted, and the
+ * difference is peeled: it yields exactly the summaries one side has and the other lacks. The bytes follow the
+ * number of differing keys, not the number of keys near them. No table is involved in either call.
+ *
+ * All arithmetic is modulo 2^64. mix64 and G are the census's (the splitmix64 finaliser, 0x9E3779B97F4A7C15).
+ *
+ * Element: a hkv_key_summary read as two little-endian words, a = bytes 0..7 (the key), b = bytes 8..15 (ts version,
+ * ts cid, state, two zero bytes).
+ * Check word: c(a, b) = mix64(mix64(a + G) + b).
+ * Sketch: 3 S cells, three subtables of S cells each, 1 <= S < 2^32; S need not be a power of two.
+ * Slot: an element's cell in subtable j (0, 1, 2) is j S + (((mix64(c + (j + 1) G) >> 32) * S) >> 32). The slots
+ * depend on c, so two versions of one key (another timestamp or state) fall into unrelated cells.
+ * Cell (hkv_sketch_cell, 32 bytes): count, key_xor, meta_xor, check_xor. Adding an element does count += 1,
+ * key_xor ^= a, meta_xor ^= b, check_xor ^= c in its three cells. The sketch of a list is the sum over its elements:
+ * a function of the multiset, whatever the list's order, the grid or the order the atomics land in, so equal lists
+ * give equal bytes.
+ * Difference: D = A - B cell by cell; the counts are subtracted, the other three words xor-ed.
+ * Pure cell: cell i of subtable j is pure when count is 1 or 2^64 - 1, c(key_xor, meta_xor) == check_xor, and the
+ * slot of the element (key_xor, meta_xor) in subtable j is i.
+ *
+ * Decode. Passes p = 0, 1, 2, ...; pass p looks at subtable p mod 3 only. Every cell of that subtable that is pure
+ * as the pass begins gives up its element: to the only_a list when count is 1, to only_b when it is 2^64 - 1. The
+ * element is then taken out of its three cells (their counts lose the pure cell's count, the other words are
+ * xor-ed); the pure cell becomes zero. Within a pass no element is taken twice, an element having one cell per
+ * subtable, and the other two subtables are only written, by commutative updates. So the cell bytes after every
+ * pass, the pass count and the two lists as sets are fixed by D alone; grid size and scheduling do not change them.
+ * The decode ends after three consecutive passes that found nothing, or at HKV_SKETCH_MAX_PASSES (a cap, not a
+ * tuning knob: 2.0 n cells decode n elements in about a dozen passes, 1.3 n cells in under fifty).
+ *
+ * Result (hkv_sketch_result, 64 bytes): only_a, only_b -- the elements taken; either may exceed its cap, elements
+ * past a cap are still taken out of the cells, and nothing is written at or past min(count, cap) * 16 bytes of a
+ * list. undecoded -- the non-zero cells left; 0: the decode is complete. passes -- the index of the last pass that
+ * took an element, plus 1; 0 when none did. exhausted -- 1 when the decode stopped at HKV_SKETCH_MAX_PASSES without
+ * three consecutive passes that found nothing (passes > HKV_SKETCH_MAX_PASSES - 3). The reserved words are zero.
+ * d_a is left holding the remainder, the 2-core of the difference.
+ *
+ * Safety. A false pure cell needs a 64-bit check collision. Even then it cannot corrupt a table: decoded summaries
+ * only feed hkv_table_need_async and hkv_table_fetch_async, which read the real tables; a bogus key comes back
+ * absent, and a bogus version of a real key fetches that key's real record, whose install is timestamp-guarded.
+ *
+ * hkv_summaries_sketch_async: one pass over n summaries into d_cells (3 * sub_cells cells). accumulate == 0: the
+ * cells are zeroed first (overwritten, not accumulated); otherwise the list is added to what is there.
+ * hkv_sketch_decode_async: d_a -= d_b, then the passes, all enqueued up front with no host read in between; a pass
+ * that follows three idle ones returns at once. d_result is overwritten. Both calls are asynchronous and ordered by
+ * `stream` alone. Refusals, with a negative code and a message in hkv_last_error() that names the call (sketch,
+ * sketch_decode), before anything is launched: a NULL cells buffer or result; a NULL buffer whose count or cap is
+ * not zero; a buffer or result that is not 16-byte aligned; sub_cells == 0 or >= 2^32.
+ *
+ * A sketch-level repair (hermes_amd.replica_group.sketch_delta_resync) is: both partition censuses and the diff;
+ * summaries of the source and of the target for the differing partitions; one sketch of each with the same S; the
+ * decode of source minus target at the target; the target's need list of only_a; the source's fetch; the install
+ * (or the upsert); the target's partition census again. It ships 96 S bytes of sketch where the key-level repair
+ * ships 16 bytes per key of the differing partitions. When undecoded != 0 the lists are dropped and the key-level
+ * exchange runs instead. Every limit of a repair holds. */
+#define HKV_SKETCH_MAX_PASSES 192
+typedef struct hkv_sketch_cell {
+    uint64_t count, key_xor, meta_xor, check_xor;
+} hkv_sketch_cell;
+typedef struct hkv_sketch_result {
+    uint64_t only_a, only_b;     /* elements taken (either may exceed its cap) */
+    uint64_t undecoded;          /* non-zero cells left */
+    uint64_t passes;             /* index of the last pass that took an element, plus 1 */
+    uint64_t exhausted;          /* 1: stopped at HKV_SKETCH_MAX_PASSES */
+    uint64_t reserved[3];        /* zero */
+} hkv_sketch_result;
+uint32_t hkv_sketch_cell_bytes(void);     /* sizeof(hkv_sketch_cell) = 32, for bindings */
+uint32_t hkv_sketch_result_bytes(void);   /* sizeof(hkv_sketch_result) = 64 */
+int hkv_summaries_sketch_async(const void *d_summaries, uint64_t n, hkv_sketch_cell *d_cells, uint64_t sub_cells,
+                               int accumulate, void *stream);
+int hkv_sketch_decode_async(hkv_sketch_cell *d_a, const hkv_sketch_cell *d_b, uint64_t sub_cells, void *d_only_a,
+                            uint64_t cap_a, void *d_only_b, uint64_t cap_b, hkv_sketch_result *d_result, void *stream);
+
 /* default table used by the reference entry points */
 int  hkv_set_default_config(const hkv_config *cfg);
 hkv_table *hkv_default_table(void);
