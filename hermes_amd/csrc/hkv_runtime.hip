@@ -1475,9 +1475,25 @@ static bool srv_exited(const hkv_table *t)
     return false;
 }
 
-// With t->hmu held: every workgroup of the serving kernel gone (it may have left by itself already)
+static void srv_ensure(hkv_table *t);
+static uint32_t part_done(const hkv_table *t);
+
+// With t->hmu held: every workgroup of the serving kernel gone (it may have left by itself already),
+// and every published launch finished in every partition. A workgroup that read its next slot's seq
+// before launch n was published and the stop word after it was raised leaves without n while its
+// neighbours take n (so does one that idled out beside them); whatever the caller then puts on the
+// stream would run before n in that partition and after n in the others, which no serial order of
+// calls explains. So the launches counted in pseq are served to the end first, by a server started
+// here if none is running. pseq only moves under hmu (held), and a launch counted there is published
+// without hmu (host_launch_part), so this wait depends on the publisher and the device alone.
 static void srv_stop_locked(hkv_table *t)
 {
+    if (t->ring)
+        for (uint32_t spins = 0; part_done(t) != t->pseq; ++spins) {
+            if (!t->srv_running || srv_exited(t)) srv_ensure(t);
+            __builtin_ia32_pause();
+            if ((spins & 255u) == 255u) sched_yield();
+        }
     if (!t->srv_running) return;
     srv_set_stop(t, 1u);
     if (hipEventSynchronize(t->srv_ev) != hipSuccess) die("serving kernel");
@@ -1619,7 +1635,8 @@ static void host_launch_part(hkv_table *t, std::unique_lock<std::mutex> &lk)
     }
     const long c0 = g_host_timing ? now_ns() : 0;
     for (uint32_t spins = 0; (int32_t)(t->pseq - part_done(t)) >= inflight; ++spins) {
-        if (serve && t->srv_running && srv_exited(t)) srv_ensure(t);   // a server that left has work to do
+        // a server that left, or was stopped, has work to do
+        if (serve && (!t->srv_running || srv_exited(t))) srv_ensure(t);
         lk.unlock();
         __builtin_ia32_pause();
         if ((spins & 255u) == 255u) sched_yield();
@@ -2033,7 +2050,9 @@ void hermes_batch_ops_to_KVS(enum hermes_batch_type_t type, uint8_t *op_array, i
             if ((spins & 1023u) == 1023u) {
                 sched_yield();
                 std::lock_guard<std::mutex> lk(t->hmu);
-                if (t->srv_running && srv_exited(t)) srv_ensure(t);   // it left before taking this launch
+                // it left, or was stopped, before taking this launch (looked at again under the lock: a
+                // server started for a launch that has finished would only sit in front of the stream)
+                if (t->ring && (int32_t)(part_done(t) - r.pseq) < 0 && (!t->srv_running || srv_exited(t))) srv_ensure(t);
             }
         }
     } else if (mode == kModeSmall) {  // the kernel's completion flag in pinned memory

@@ -10,6 +10,11 @@
   disjoint keys, so any interleaving gives every key the same history: each thread's recorded
   calls (inputs, outputs, read_write_ops) are replayed one after another on the oracle and must
   match byte for byte.
+* tools/capi_threads contend: 8 threads contending on 48 shared keys with nothing held, their batches
+  switching between the serving kernel's ring, the mixed single-workgroup launch and the multi-kernel
+  engine while a control call stops the serving kernel at arbitrary moments. tests/serial_order.py
+  must find a serial order of the recorded calls, real-time order kept, that the oracle reproduces
+  byte for byte, final log included.
 """
 import json
 import os
@@ -24,6 +29,7 @@ torch = pytest.importorskip("torch")
 
 from hermes_amd import layout as L  # noqa: E402
 from oracle.oracle import OracleKVS, gen_keys  # noqa: E402
+from tests.serial_order import Call, contention, find_serial_order  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOLS = os.path.join(ROOT, "tools")
@@ -99,6 +105,62 @@ def test_concurrent_callers_match_oracle(tmp_path, env):
             if t == int(L.BatchType.local_ops):
                 n_put += int((eout.reshape(n, esz)[:, 9] == int(L.Resp.PUT_SUCCESS)).sum())
     assert n_put > 0
+
+
+# which launch paths a variant of SWITCHES has: the serving kernel runs only over device-staged batches
+# (the default and the merge/inflight variant), HKV_HOST_PART=0 never partitions a launch
+def _paths(env):
+    part = env.get("HKV_HOST_PART") != "0"
+    return part, part and "HKV_HOST_SERVE" not in env and "HKV_STAGE_VRAM" not in env
+
+
+@pytest.mark.parametrize("env", SWITCHES, ids=lambda e: ",".join(f"{k}={v}" for k, v in e.items()) or "default")
+def test_contending_callers_have_a_serial_order(tmp_path, env):
+    """results are those of the reference applying the calls in some order of the callers
+    that keeps each caller's program order (and real time: a call that returned before another began
+    precedes it). Eight threads on 48 shared keys, five of them workers, two peers and one sending
+    batches that take the mixed launch and the engine, nothing held; the order is recovered from the
+    outputs by tests/serial_order.py on the oracle, and the device's log must equal the oracle's."""
+    threads, rounds = 8, 30
+    p = subprocess.run([os.path.join(TOOLS, "capi_threads"), "contend", str(threads), str(rounds), str(tmp_path)],
+                       capture_output=True, text=True, timeout=120, env=dict(os.environ, HKV_TRACE="1", **env))
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    print(d)
+    assert d["error_flags"] == 0 and d["control_calls"] > 0
+    calls = []
+    for k in range(threads):
+        times = np.fromfile(os.path.join(tmp_path, f"thread{k}.times"), np.int64).reshape(-1, 2)
+        recs = _read_calls(os.path.join(tmp_path, f"thread{k}.bin"))
+        assert len(recs) == len(times) >= rounds
+        calls.append([Call(*r, int(t0), int(t1)) for r, (t0, t1) in zip(recs, times)])
+    n = sum(len(c) for c in calls)
+    assert n == d["calls"]
+    final_log = np.fromfile(os.path.join(tmp_path, "final_log.bin"), np.uint8)
+    assert len(final_log) == 64_000_000
+    o = OracleKVS(1 << 21, 1 << 30, machine_id=0)
+    o.populate(1_000_000, L.DEFAULT.kvs_value)
+    order, applications = find_serial_order(calls, o, L.membership(3, 0), final_log)   # within 4*T*N applications
+    print(f"{n} calls, {applications} applications ({applications / n:.2f} per call)")
+    assert len(order) == n
+    # the run was worth checking: calls overlapped calls of other threads on shared keys, every response occurred
+    share, seen = contention(calls)
+    print(f"{share:.2f} of the calls overlap a call of another thread that shares a key")
+    assert share > 0.5
+    R, B = L.Resp, L.BatchType
+    wanted = {(int(B.local_ops), int(R.GET_COMPLETE)), (int(B.local_ops), int(R.GET_STALL)),
+              (int(B.local_ops), int(R.PUT_SUCCESS)), (int(B.local_ops), int(R.PUT_STALL)),
+              (int(B.acks), int(R.ACK_SUCCESS)), (int(B.acks), int(R.LAST_ACK_SUCCESS)),
+              (int(B.invs), int(R.INV_SUCCESS)), (int(B.vals), int(R.VAL_SUCCESS))}
+    assert wanted <= seen, sorted(wanted - seen)
+    # and it went down the paths it is for (TRACE lines of hkv_runtime.hip)
+    part, serving = _paths(env)
+    trace = p.stderr
+    assert trace.count("] mixed launch") >= 1 and trace.count("] combined launch") >= 1
+    if part:
+        assert trace.count("] partitioned launch") >= 1
+    if serving:
+        assert trace.count("] serving kernel epoch") >= 2   # the second is a restart
 
 
 def test_mixed_batches_on_shared_keys_match_oracle(tmp_path):
