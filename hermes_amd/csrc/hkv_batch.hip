@@ -1423,10 +1423,16 @@ __global__ __launch_bounds__(64) void k_unique_lds(BatchArgs a)
 // and each element and the entry line are written back where they changed. An ACK's completion finds
 // its read_write_ops once per position (the rows share the batch layout).
 // No SGPR or occupancy attribute: 80 SGPRs and 8 waves per SIMD were within box noise.
-template <int TYPE, int RMAX, int CH, bool IL = false>
+//
+// A packed ACK launch finds its positions' batches as the block's first loads, beside the element loads and the
+// lookup, not after the resolve ("The ACK rows launch"): the wave narrows the offsets to a window
+// around the block's first position (kary_last_le, two coalesced loads for up to 2^18 batches), keeps the
+// window, one offset per lane twice, and every lane reads its own position's batch from it
+// (rows_window_batch). A position past the window, after a long run of empty batches, asks batch_of as before.
+// P: positions per lane group; 2, or 4 for a round's ACK launch at configs[1] (launch_rows).
+template <int TYPE, int RMAX, int CH, int P = kLookupPair, bool IL = false>
 __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
 {
-    constexpr int P = kLookupPair;
     constexpr int E = 16 * P;   // positions per wave: P per lane group
     // CH: 16-B chunks of an element held in LDS (1 for 16-B ACKs, 4 for 56-B INVs)
     __shared__ uint4 sops[RMAX][E * CH];
@@ -1438,23 +1444,62 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
     const int R = a.n_rows < RMAX ? a.n_rows : RMAX;
     // packed rows may end before the stride: elements past the last batch offset are in no batch
     const int64_t n_live = a.offsets ? (int64_t)a.offsets[a.n_batches] : a.n;
+    const auto is_live = [&](int64_t i) { return i < a.n && i < n_live && (a.offsets || in_count(a, (uint32_t)i)); };
     uint64_t key[P];
     bool probe[P], ok[P], live[P];
     uint64_t phys[P];
-    uint4 ln[P], op[RMAX][P];
+    // FLAT (the four-position instance, 16-B elements): lane t loads and writes back position t's element of
+    // every row -- 4 VGPRs a row, not 4 for each of the lane group's positions -- and the lane groups read the
+    // headers from LDS
+    constexpr bool FLAT = P == 4 && CH == 1;
+    const bool flat_live = FLAT && is_live(i0 + tid);
+    uint4 ln[P], op[RMAX][FLAT ? 1 : P];
     uint32_t part[P];
     int te[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         te[k] = k * 16 + (tid >> 2);
-        const int64_t i = i0 + te[k];
-        live[k] = i < a.n && i < n_live && (a.offsets || in_count(a, (uint32_t)i));
+        live[k] = is_live(i0 + te[k]);
+    }
+    if (FLAT) {
 #pragma unroll
         for (int r = 0; r < RMAX; ++r) {
-            const bool on = live[k] && r < R && r != a.skip_row;
-            op[r][k] = on && q < CH ? load_chunk(a.elems + (r * a.row_stride + i) * a.esz, q, a.esz)
-                                    : make_uint4(0u, 0u, 0u, 0u);
-            if (q < CH) sops[r][te[k] * CH + q] = op[r][k];
+            const bool on = flat_live && r < R && r != a.skip_row;
+            op[r][0] = on ? load_chunk(a.elems + (r * a.row_stride + i0 + tid) * a.esz, 0, a.esz) : make_uint4(0u, 0u, 0u, 0u);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < (FLAT ? 1 : P); ++k) {
+            const int64_t i = i0 + te[k];
+#pragma unroll
+            for (int r = 0; r < RMAX; ++r) {
+                const bool on = live[k] && r < R && r != a.skip_row;
+                op[r][k] = on && q < CH ? load_chunk(a.elems + (r * a.row_stride + i) * a.esz, q, a.esz)
+                                        : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+    }
+    // (packed ACK launches) the batch search's first step, in flight beside the elements; all of it is the wave's
+    const bool locate = TYPE == kAcks && a.offsets && a.rw;
+    int32_t blo = 0, bhi = a.n_batches - 1, bsample = 0;
+    const auto sample = [&]() {   // this lane's sample of the step, INT32_MAX past the range
+        const int32_t s = kary_sample(blo, bhi, tid);
+        const int32_t v = a.offsets[s < bhi ? s : bhi];
+        return s <= bhi ? v : INT32_MAX;
+    };
+    const auto narrow = [&]() { kary_narrow(blo, bhi, __popcll(__ballot((int64_t)bsample <= i0))); };
+    const bool step1 = locate && bhi - blo >= kRowsWindow / 2;
+    if (step1) bsample = sample();
+    if (FLAT) {
+#pragma unroll
+        for (int r = 0; r < RMAX; ++r) sops[r][tid] = op[r][0];
+        __syncthreads();
+    } else {
+#pragma unroll
+        for (int k = 0; k < (FLAT ? 1 : P); ++k) {
+#pragma unroll
+            for (int r = 0; r < RMAX; ++r)
+                if (q < CH) sops[r][te[k] * CH + q] = op[r][k];
         }
     }
 #pragma unroll
@@ -1464,9 +1509,17 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
         bool mismatch = false;
 #pragma unroll
         for (int r = 0; r < RMAX; ++r) {
-            const uint64_t kr = (uint64_t)(uint32_t)__shfl((int)op[r][k].x, 0, 4) |
-                                ((uint64_t)(uint32_t)__shfl((int)op[r][k].y, 0, 4) << 32);
-            const uint32_t h0 = (uint32_t)__shfl((int)op[r][k].z, 0, 4);
+            uint64_t kr;
+            uint32_t h0;
+            if (FLAT) {
+                const uint4 h = sops[r][te[k]];
+                kr = (uint64_t)h.x | ((uint64_t)h.y << 32);
+                h0 = h.z;
+            } else {
+                const uint4 &h = op[r][FLAT ? 0 : k];
+                kr = (uint64_t)(uint32_t)__shfl((int)h.x, 0, 4) | ((uint64_t)(uint32_t)__shfl((int)h.y, 0, 4) << 32);
+                h0 = (uint32_t)__shfl((int)h.z, 0, 4);
+            }
             if (!live[k] || r >= R || r == a.skip_row || (uint8_t)h0 == 0) continue;   // a hole
             if (skip_elem_os(TYPE, (uint8_t)h0, (uint8_t)(h0 >> 8))) continue;
             if (p && kr != kk) mismatch = true;
@@ -1479,7 +1532,24 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
         probe[k] = part[k] != 0;
     }
     uint8_t *home[P];   // (IL) where each hit's entry bytes live
-    lookup_pair<P, IL>(a, key, probe, q, gbase, ok, phys, ln, home);
+    // the search's second step rides with the bucket loads, the window with the log lines
+    bool step2 = false;
+    lookup_pair_beside<P, IL>(a, key, probe, q, gbase, ok, phys, ln, home, [&]() {
+        if (step1) narrow();
+        step2 = locate && bhi - blo >= kRowsWindow / 2;
+        if (step2) bsample = sample();
+    });
+    if (step2) narrow();
+    while (locate && bhi - blo >= kRowsWindow / 2) {   // more than 2^18 batches
+        bsample = sample();
+        narrow();
+    }
+    // offsets blo .. blo + 127 (INT32_MAX where no batch is), two per lane
+    int32_t w0 = INT32_MAX, w1 = INT32_MAX;
+    if (locate) {
+        if (blo + tid < a.n_batches) w0 = a.offsets[blo + tid];
+        if (blo + 64 + tid < a.n_batches) w1 = a.offsets[blo + 64 + tid];
+    }
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         Meta m;
@@ -1490,6 +1560,14 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
             sent[te[k]] = hit ? (uint32_t)(phys[k] / a.g.entry_unit) : kNone;
             spart[te[k]] = (uint8_t)part[k];
         }
+    }
+    // lane t's position is i0 + t: its batch, or -1 (the window ended first, or there is nothing to locate)
+    int32_t pb = -1;
+    if (locate) {
+        const int32_t k0 = __popcll(__ballot((int64_t)w0 <= i0)) - 1;   // the block's first batch, in the first 64
+        const auto win = [&](int32_t j) { return __builtin_amdgcn_readlane(j < 64 ? w0 : w1, j & 63); };
+        int32_t b;
+        if (rows_window_batch(win, blo, k0 > 0 ? k0 : 0, i0 + tid, i0 + E - 1, b)) pb = b;
     }
     __syncthreads();
     if (tid < E && i0 + tid < n_live) {
@@ -1514,9 +1592,13 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
                 if ((p >> r) & 1u) dispatch<31>(TYPE, reinterpret_cast<uint8_t *>(&sops[r][tid * CH]), ent, 0, t, c);
             if (!meta_equal(t, m)) meta_store(ent, t);
             if (TYPE == kAcks && done >= 0 && a.rw) {
-                uint8_t *xx;
-                uint8_t idx;
-                elem_at(a, (uint32_t)i, xx, idx, c);
+                if (pb >= 0) {
+                    batch_rw(a, pb, c);
+                } else {
+                    uint8_t *xx;
+                    uint8_t idx;
+                    elem_at(a, (uint32_t)i, xx, idx, c);
+                }
                 complete_rw_slot(c, done);
             }
         } else {
@@ -1526,29 +1608,38 @@ __global__ __launch_bounds__(64) void k_unique_rows(BatchArgs a)
         }
     }
     __syncthreads();
+    // chunk c of row r's element at position pos goes back where it differs from what was loaded (was)
+    const auto put_back = [&](int r, int pos, int c, const uint4 &was) {
+        uint4 w = sops[r][pos * CH + c];
+        if (TYPE == kAcks && CH == 1 && a.ack_out) {
+            // the VAL callbacks (hermes_worker.c:122-157, as shipped): an element whose opcode is not
+            // ACK_SUCCESS, MEMBERSHIP_CHANGE or EMPTY is sent as a VAL from this machine, every
+            // non-empty one leaves empty; a hole (opcode 0) is no element
+            const uint8_t oc = (uint8_t)w.z;
+            uint4 v = make_uint4(0u, 0u, (uint32_t)kEmpty, 0u);
+            if (oc != 0 && oc != kAckSuccess && oc != kOpMembChange && oc != kEmpty)
+                v = make_uint4(w.x, w.y, (w.z & ~0xFFFFu) | (uint32_t)kOpVal | ((uint32_t)(uint8_t)a.g.machine_id << 8), w.w);
+            *reinterpret_cast<uint4 *>(a.ack_out + (r * a.row_stride + i0 + pos) * 16) = v;
+            if (oc != 0 && oc != kEmpty) w.z = (w.z & ~0xFFu) | (uint32_t)kEmpty;
+        }
+        if (!chunk_equal(w, was)) {
+            uint8_t *xg = a.elems + (r * a.row_stride + i0 + pos) * a.esz + 16 * c;
+            if (16 * c + 16 <= a.esz) *reinterpret_cast<uint4 *>(xg) = w;
+            else *reinterpret_cast<uint64_t *>(xg) = (uint64_t)w.x | ((uint64_t)w.y << 32);
+        }
+    };
+    if (FLAT && flat_live) {
+#pragma unroll
+        for (int r = 0; r < RMAX; ++r)
+            if (r < R && r != a.skip_row) put_back(r, tid, 0, op[r][0]);
+    }
 #pragma unroll
     for (int k = 0; k < P; ++k) {
         if (!live[k]) continue;
 #pragma unroll
         for (int r = 0; r < RMAX; ++r) {
-            if (r >= R || r == a.skip_row || q >= CH) continue;
-            uint4 w = sops[r][te[k] * CH + q];
-            if (TYPE == kAcks && CH == 1 && a.ack_out) {
-                // the VAL callbacks (hermes_worker.c:122-157, as shipped): an element whose opcode is not
-                // ACK_SUCCESS, MEMBERSHIP_CHANGE or EMPTY is sent as a VAL from this machine, every
-                // non-empty one leaves empty; a hole (opcode 0) is no element
-                const uint8_t oc = (uint8_t)w.z;
-                uint4 v = make_uint4(0u, 0u, (uint32_t)kEmpty, 0u);
-                if (oc != 0 && oc != kAckSuccess && oc != kOpMembChange && oc != kEmpty)
-                    v = make_uint4(w.x, w.y, (w.z & ~0xFFFFu) | (uint32_t)kOpVal | ((uint32_t)(uint8_t)a.g.machine_id << 8), w.w);
-                *reinterpret_cast<uint4 *>(a.ack_out + (r * a.row_stride + i0 + te[k]) * 16) = v;
-                if (oc != 0 && oc != kEmpty) w.z = (w.z & ~0xFFu) | (uint32_t)kEmpty;
-            }
-            if (!chunk_equal(w, op[r][k])) {
-                uint8_t *xg = a.elems + (r * a.row_stride + i0 + te[k]) * a.esz + 16 * q;
-                if (16 * q + 16 <= a.esz) *reinterpret_cast<uint4 *>(xg) = w;
-                else *reinterpret_cast<uint64_t *>(xg) = (uint64_t)w.x | ((uint64_t)w.y << 32);
-            }
+            if (FLAT || r >= R || r == a.skip_row || q >= CH) continue;
+            put_back(r, te[k], q, op[r][FLAT ? 0 : k]);
         }
         if (ok[k] && q > 0) {   // bytes 0..15 of a log line (the MICA key) never change
             const uint4 l = sln[te[k] * 4 + q];
@@ -2701,14 +2792,33 @@ static BatchArgs make_args(const BatchLaunch &bl, const BatchPlan &p)
 // ---- the engines' launchers; each returns 0 or launch_batch's -3
 // k_unique_rows: two positions per lane group, 32 per wave
 constexpr int kRowsElems = 16 * kLookupPair;   // positions per k_unique_rows block (its E)
+// From kRowsWidePositions on, two-row launches of 16-B ACKs take four positions per lane group, 64 per wave.
+// The two-position instance holds 28 blocks on a CU (hipOccupancyMaxActiveBlocksPerMultiprocessor; 7 waves per
+// SIMD), 7,168 on the chip's 256 CUs: up to 7,168 * 32 positions every block is resident at once, and smaller
+// blocks mean more chains in flight per position. One block more starts only when a first one retires and pays
+// the whole dependent chain again on an emptying chip -- a round's ACK launch at configs[1] was 8,390 such
+// blocks, 38.4-39.6 us against 34.0 in 4,198 blocks of 64 (5 waves per SIMD, 5,120 resident;
+// profiles/ack_rows_kernels.txt, profiles/ack_rows_registers.txt).
+constexpr int kRowsWideElems = 16 * 4;
+constexpr int64_t kRowsWidePositions = (int64_t)28 * 256 * kRowsElems + 1;
 template <int T, int CH>
 static void launch_rows(const BatchArgs &a, const BatchPlan &p, hipStream_t s)
 {
     const unsigned lgrid = (unsigned)((a.n + kRowsElems - 1) / kRowsElems);
     with_bool(p.il, [&](auto il) {
         constexpr bool IL = decltype(il)::value;
-        if (p.rmax == 2) hipLaunchKernelGGL((k_unique_rows<T, 2, CH, IL>), dim3(lgrid), dim3(64), 0, s, a);
-        else hipLaunchKernelGGL((k_unique_rows<T, 8, CH, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        if constexpr (T == kAcks && CH == 1) {
+            if (p.rmax == 2 && a.n >= kRowsWidePositions) {
+                const unsigned wgrid = (unsigned)((a.n + kRowsWideElems - 1) / kRowsWideElems);
+                hipLaunchKernelGGL((k_unique_rows<T, 2, CH, 4, IL>), dim3(wgrid), dim3(64), 0, s, a);
+                return;
+            }
+        }
+        if (p.rmax == 2) {
+            hipLaunchKernelGGL((k_unique_rows<T, 2, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        } else {
+            hipLaunchKernelGGL((k_unique_rows<T, 8, CH, kLookupPair, IL>), dim3(lgrid), dim3(64), 0, s, a);
+        }
     });
 }
 

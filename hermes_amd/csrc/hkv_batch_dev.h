@@ -233,6 +233,56 @@ __device__ __forceinline__ int32_t batch_of(const BatchArgs &a, int64_t i, int64
     return lo;
 }
 
+// batch_of's search for a whole wave (k_unique_rows): a 64-ary search over the n offsets that narrows
+// [lo, hi] -- offsets[lo] <= i, the answer within -- until at most `span` batches follow lo, and returns lo.
+// Each step samples lo + step, lo + 2 step, .. lo + 64 step (kary_sample); count(lo, hi) says how many of the
+// samples at or below hi hold an offset <= i (a prefix: offsets ascend), which a wave answers with one coalesced
+// load and a ballot and a host loop by looking. span 0 is batch_of itself; span 63 leaves the rest to a
+// window of the offsets from lo on (rows_window_batch): two steps for up to 2^18 batches, against 18.
+constexpr int kRowsWindow = 128;   // offsets lo .. lo + 127: the block's first batch is among the first 64
+__host__ __device__ inline int32_t kary_stride(int32_t lo, int32_t hi) { return (hi - lo + 63) >> 6; }
+// sample s (0 .. 63) of a step, and the range after c of the step's samples were in range and <= i
+__host__ __device__ inline int32_t kary_sample(int32_t lo, int32_t hi, int s) { return lo + (s + 1) * kary_stride(lo, hi); }
+__host__ __device__ inline void kary_narrow(int32_t &lo, int32_t &hi, int32_t c)
+{
+    const int32_t step = kary_stride(lo, hi);
+    lo += c * step;
+    if (lo + step - 1 < hi) hi = lo + step - 1;
+}
+template <class Count>
+__host__ __device__ inline int32_t kary_last_le(int32_t n, int32_t span, Count &&count)
+{
+    int32_t lo = 0, hi = n - 1;
+    while (hi - lo > span) kary_narrow(lo, hi, count(lo, hi));
+    return lo;
+}
+
+// The batch of position i from the window win(k) = offsets[lo + k] (k < kRowsWindow; a k whose batch does not
+// exist reads as INT32_MAX), scanned from k0 (win(k0) <= i, or k0 == 0): lo + the last k with win(k) <= i.
+// The scan ends at the first offset above i_max >= i, so a wave that passes its last position's i_max runs it
+// in step, k and win(k) the same in every lane. False when the window may end before i's batch (a run of
+// empty batches): the caller asks batch_of.
+template <class Win>
+__host__ __device__ inline bool rows_window_batch(Win &&win, int32_t lo, int32_t k0, int64_t i, int64_t i_max, int32_t &b)
+{
+    int32_t k = k0;
+    for (int32_t j = k0 + 1; j < kRowsWindow; ++j) {
+        const int32_t v = win(j);
+        if ((int64_t)v > i_max) break;
+        if ((int64_t)v <= i) k = j;
+    }
+    b = lo + k;
+    return k + 1 < kRowsWindow;
+}
+
+// The read_write_ops of batch b and its mirrors
+__device__ __forceinline__ void batch_rw(const BatchArgs &a, int32_t b, Ctx &c)
+{
+    c.rw = a.rw ? a.rw + (int64_t)b * a.rw_stride : nullptr;
+    c.rws = a.rws ? a.rws + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
+    c.rwo = a.rwo ? a.rwo + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
+}
+
 __device__ __forceinline__ void elem_at(const BatchArgs &a, uint32_t i, uint8_t *&x, uint8_t &idx, Ctx &c)
 {
     c.rw = nullptr;
@@ -242,9 +292,7 @@ __device__ __forceinline__ void elem_at(const BatchArgs &a, uint32_t i, uint8_t 
         int64_t start;
         const int32_t b = batch_of(a, i, start);
         idx = (uint8_t)(i - start);
-        c.rw = a.rw ? a.rw + (int64_t)b * a.rw_stride : nullptr;
-        c.rws = a.rws ? a.rws + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
-        c.rwo = a.rwo ? a.rwo + (int64_t)b * (a.rw_stride / a.g.op_size) : nullptr;
+        batch_rw(a, b, c);
     }
     x = a.elems + (int64_t)i * a.esz;
 }
@@ -363,10 +411,15 @@ constexpr int kLookupPair = 2;
 // 16 B of the second half -- the inline key's entry -- in the same step; a hit on the flagged slot takes those
 // bytes, any other hit loads the log line as before. home: where the hit's entry bytes live (writes go there);
 // inl: the hit is its bucket's inline key. phys stays the log offset either way (the key's identity).
-template <int P = kLookupPair, bool IL = false, bool F = false>
+// beside: the caller's own work between the issue of the bucket loads and their first use (its loads ride
+// along with them: k_unique_rows' batch search)
+struct NothingBeside {
+    __device__ __forceinline__ void operator()() const {}
+};
+template <int P = kLookupPair, bool IL = false, bool F = false, class Beside = NothingBeside>
 __device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
                                             int gbase, bool *ok, uint64_t *phys, uint4 *ln, unsigned long long *fwv,
-                                            uint8_t **home, bool *inl)
+                                            uint8_t **home, bool *inl, Beside &&beside = Beside{})
 {
     uint4 v[P], ev[P];
 #pragma unroll
@@ -379,6 +432,7 @@ __device__ __forceinline__ void lookup_core(const BatchArgs &a, const uint64_t *
             v[k] = probe[k] ? bucket_words(a.index, bucket_of(a.g, key[k]))[q] : make_uint4(0u, 0u, 0u, 0u);
         }
     }
+    beside();
     bool il[P];
 #pragma unroll
     for (int k = 0; k < P; ++k) {
@@ -421,6 +475,14 @@ __device__ __forceinline__ void lookup_pair(const BatchArgs &a, const uint64_t *
                                             bool *inl = nullptr)
 {
     lookup_core<P, IL, false>(a, key, probe, q, gbase, ok, phys, ln, nullptr, home, inl);
+}
+
+template <int P, bool IL, class Beside>
+__device__ __forceinline__ void lookup_pair_beside(const BatchArgs &a, const uint64_t *key, const bool *probe, int q,
+                                                   int gbase, bool *ok, uint64_t *phys, uint4 *ln, uint8_t **home,
+                                                   Beside &&beside)
+{
+    lookup_core<P, IL, false>(a, key, probe, q, gbase, ok, phys, ln, nullptr, home, nullptr, beside);
 }
 
 // lookup_pair that also loads each hit's F word beside its log line (lane q == 0; ~0 for a miss), so a
